@@ -17,7 +17,15 @@ fails and exits with that rank's code.
 
 Rank 0 prints one JSON line; ``value`` is the whole-job tokens/s (global tokens / max-over-ranks time).
 The line also carries what the ranks saw: the world size of the process group, every rank's step time,
-and whether the parameters of all data-parallel replicas agree bit-for-bit after the last step.
+and whether the parameters of all data-parallel replicas agree bit-for-bit after the last step (one pass
+over the parameters, a fraction of a step).
+
+A plain run sets up, warms up, times the steps and prints that line; it runs nothing else.  Measurements
+that need runs of their own (other precisions or shapes, the reference, per-kernel figures) live in
+``tools/`` and are not started from here; ``--full`` is where any such extra of this file belongs (today
+there is none, so it changes nothing).  ``--dump-outputs DIR`` writes what the last timed step returned,
+and a seeded sample of the parameters it left behind, as ``DIR/<name>.npy``: inputs and initial weights
+are seeded, so two builds can be compared output for output.
 
 ``--backend gloo`` runs the same path on CPU processes (plumbing mode for the CPU test-suite);
 ``--backend gloo-gpu`` runs GPU ranks (several may share one GPU, which RCCL refuses) with gloo collectives
@@ -97,6 +105,12 @@ def _args(argv: Optional[list[str]] = None) -> argparse.Namespace:
                    help="hipBLASLt solution table (scaling_amd/tuning/gemm_gfx950.csv); tune = benchmark and write")
     p.add_argument("--gemm-tuning-out", type=str, default=None)
     p.add_argument("--profile-json", type=str, default=None, help="write per-step times to this file")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, rank 0 writes what the last timed train step returned (loss, gradient "
+                        "norm, scalar metrics) and a fixed seeded sample of the parameters it left behind to DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run whatever this benchmark measures beyond its headline figure (today nothing: the "
+                        "side measurements are separate programs under tools/)")
     p.add_argument("--launch-timeout", type=float, default=3000.0, help="launcher: kill all ranks after this many s")
     argv = sys.argv[1:] if argv is None else argv
     return apply_example(apply_shard_proxy(apply_preset(p.parse_args(argv), argv), argv), argv)
@@ -387,6 +401,39 @@ def _param_checksum(model: Any, device: Any) -> Any:
     return acc
 
 
+DUMP_SAMPLE_PER_TENSOR = 16384  # 16 MB of float32 over the 291 tensors of the 7B shape; a dump stays under 64 MB
+
+
+def _dump_outputs(out_dir: str, last: Any, model: Any) -> None:
+    """``--dump-outputs``: what a caller of the timed path receives from its last step, as ``<name>.npy``.
+
+    ``train_step`` returns scalars (loss, gradient norm, metrics: float64 files) and leaves the updated parameters
+    behind: of every parameter tensor of this rank, the elements at ``DUMP_SAMPLE_PER_TENSOR`` indices drawn once from
+    a fixed seed (the whole tensor when it is smaller), concatenated in ``model.parameters()`` order (float32)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    scalars = {"loss": last.loss, "global_grad_norm": last.global_grad_norm}
+    for k, v in (last.metrics or {}).items():
+        if isinstance(v, (int, float)):
+            scalars["metric_" + "".join(c if c.isalnum() else "_" for c in k)] = v
+    for name, v in scalars.items():
+        if v is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float64))
+    g = torch.Generator().manual_seed(20240)
+    parts = []
+    with torch.no_grad():
+        for p in model.parameters():
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE_PER_TENSOR:
+                idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE_PER_TENSOR,), generator=g)
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu())
+    sample = torch.cat(parts).numpy() if parts else np.zeros(0, dtype=np.float32)
+    np.save(os.path.join(out_dir, "params_sample.npy"), sample)
+
+
 def _worker(a: argparse.Namespace) -> None:
     import torch
     import torch.distributed as dist
@@ -577,6 +624,8 @@ def _worker(a: argparse.Namespace) -> None:
     dist.all_reduce(times)
     sec = float(times.max().item())
     optimizer.wait_param_sync()
+    if a.dump_outputs and rank == 0 and last is not None:
+        _dump_outputs(a.dump_outputs, last, model)
     ck = _param_checksum(model, dev)
     cks = [torch.zeros_like(ck) for _ in range(dp)]
     dist.all_gather(cks, ck, group=topology.data_parallel_group)

@@ -50,6 +50,33 @@ def test_bench_self_launch_gloo(layout):
     assert "NOT headline" in res["config"]["model"]
 
 
+def test_bench_dump_outputs_gloo(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's loss / gradient norm (float64) and the seeded parameter sample
+    (float32) as ``DIR/<name>.npy``; a second run with the same arguments (here with ``--full``, which a plain run
+    must not need) starts from the same inputs and weights and so dumps the same values; ``--steps`` is the number of
+    timed steps (the parameters after 1 and after 2 timed steps differ)."""
+    import numpy as np
+
+    dumps = {}
+    for tag, extra in (("a", ["--steps", "2"]), ("b", ["--steps", "2", "--full"]), ("one", ["--steps", "1"])):
+        d = tmp_path / tag
+        r = _run(["--gpus", "1", "--model", "llama_tiny", "--backend", "gloo", "--seq-len", "64", "--micro-batch", "1",
+                  "--warmup", "1", *extra, "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-4000:]
+        res = _json_lines(r.stdout)[0]
+        assert res["steps"] == int(extra[1]) and res["ms_per_step"] > 0
+        dumps[tag] = {f.stem: np.load(f) for f in sorted(d.glob("*.npy"))}
+        assert {"loss", "global_grad_norm", "params_sample"} <= set(dumps[tag])
+        assert all(v.dtype in (np.float32, np.float64) for v in dumps[tag].values())
+        assert sum(v.nbytes for v in dumps[tag].values()) <= 64 * 2**20
+        assert float(dumps[tag]["loss"]) == res["config"]["loss"]
+        assert dumps[tag]["params_sample"].size > 0 and np.isfinite(dumps[tag]["params_sample"]).all()
+    assert set(dumps["a"]) == set(dumps["b"])
+    for k in dumps["a"]:
+        np.testing.assert_allclose(dumps["b"][k], dumps["a"][k], rtol=1e-5, atol=1e-6, err_msg=k)
+    assert not np.array_equal(dumps["one"]["params_sample"], dumps["a"]["params_sample"])
+
+
 def test_bench_lora_gloo():
     r = _run(["--gpus", "2", "--lora", "--lora-rank", "8", "--grad-acc", "2", *TINY])
     assert r.returncode == 0, r.stderr[-4000:]

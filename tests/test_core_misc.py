@@ -10,7 +10,7 @@ import torch
 from tests.dist_utils import make_topology, run_distributed
 
 pytestmark = pytest.mark.cpu
-REF = Path("/root/reference")
+GOLDEN = Path(__file__).resolve().parent / "golden"
 
 
 # ---------------------------------------------------------------- config
@@ -57,11 +57,10 @@ def test_topology_config_rejects_inconsistent_batch():
                        micro_batch_size=4, gradient_accumulation_steps=1)
 
 
-@pytest.mark.skipif(not (REF / "examples/transformer_example/config.yml").exists(), reason="reference not mounted")
 def test_reference_transformer_config_loads_unchanged():
     from scaling_amd.transformer import TransformerConfig
 
-    cfg = TransformerConfig.from_yaml(REF / "examples/transformer_example/config.yml")
+    cfg = TransformerConfig.from_yaml(GOLDEN / "reference_transformer_example_config.yml")
     assert cfg.transformer_architecture.hidden_size == 256
     again = TransformerConfig.from_dict(json.loads(json.dumps(cfg.as_dict())))
     a, b = again.as_dict(), cfg.as_dict()

@@ -9,8 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests.golden_files import FILES as REF
+
 pytestmark = pytest.mark.cpu
-REF = Path("/root/reference/tests/transformer/files")
 
 
 def _mmap(tmp: Path, docs: list) -> Path:
@@ -78,7 +79,6 @@ def test_native_text_index_matches_reference_algorithm(seq, only_full, every_n):
     assert got == [[list(t) for t in item] for item in ref]
 
 
-@pytest.mark.skipif(not (REF / "dataset" / "data.bin").exists(), reason="reference fixtures not mounted")
 def test_text_dataset_index_bit_identical_to_reference_cache(tmp_path):
     from scaling_amd.transformer.data import TextDataset
 
@@ -98,7 +98,6 @@ def test_text_dataset_index_bit_identical_to_reference_cache(tmp_path):
     assert torch.equal(batch.input_token_ids[:, 1:], batch.target_token_ids[:, :-1])
 
 
-@pytest.mark.skipif(not (REF / "dataset" / "legacy").exists(), reason="reference fixtures not mounted")
 def test_legacy_dataset_and_blend(tmp_path):
     from scaling_amd.core import BlendedDatasetConfig
     from scaling_amd.transformer.data import LegacyBlendedDataset, TextDataset
@@ -213,7 +212,6 @@ def test_dataloader_sharding_and_resume():
     assert torch.cat([next(dl) for _ in range(2)]).tolist() == seen[0][12:20]
 
 
-@pytest.mark.skipif(not (REF / "llama2-tokenizer.json").exists(), reason="reference tokenizer not mounted")
 def test_finetuning_datasets(tmp_path):
     from scaling_amd.transformer.data import FinetuningChatDataset, FinetuningTextDataset
     from scaling_amd.transformer.tokenizer import load_tokenizers

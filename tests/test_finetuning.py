@@ -15,13 +15,10 @@ import pytest
 import torch
 
 from tests.dist_utils import free_port
+from tests.golden_files import FILES, TOKENIZER
 
 pytestmark = pytest.mark.cpu
 ROOT = Path(__file__).resolve().parent.parent
-FILES = Path("/root/reference/tests/transformer/files")
-TOKENIZER = FILES / "llama2-tokenizer.json"
-needs_fixtures = pytest.mark.skipif(not (FILES / "dataset" / "finetuning.json").exists() or not TOKENIZER.exists(),
-                                    reason="reference fixtures not mounted")
 
 
 def _config(tmp: Path, mp: int, pp: int, world: int, mbs: int = 2, acc: int = 1, memory_map: bool = False,
@@ -105,7 +102,6 @@ def _compare(tmp: Path, marker: str, skip_suffix=None, layer_filter=None) -> int
     return found
 
 
-@needs_fixtures
 @pytest.mark.parametrize("mp,pp,world", [(1, 1, 1), (1, 2, 2), (2, 1, 2)])
 def test_softprompt_finetuning(tmp_path, mp, pp, world):
     cfg = _config(tmp_path, mp, pp, world)
@@ -117,7 +113,6 @@ def test_softprompt_finetuning(tmp_path, mp, pp, world):
     assert _compare(tmp_path, "softprompt_finetuning") > 0
 
 
-@needs_fixtures
 @pytest.mark.parametrize("mp,pp,world", [(1, 1, 1), (2, 1, 2)])
 @pytest.mark.parametrize("kernel", ["torch", "flash_attention"])
 def test_adapter_finetuning(tmp_path, mp, pp, world, kernel):
@@ -133,7 +128,6 @@ def test_adapter_finetuning(tmp_path, mp, pp, world, kernel):
     assert _compare(tmp_path, "adapter_finetuning", layer_filter="TransformerLayer") > 0
 
 
-@needs_fixtures
 @pytest.mark.parametrize("mp,pp,world", [(1, 1, 1), (1, 2, 2)])
 @pytest.mark.parametrize("memory_map", [False, True])
 def test_bitfit_finetuning(tmp_path, mp, pp, world, memory_map):
@@ -147,7 +141,6 @@ def test_bitfit_finetuning(tmp_path, mp, pp, world, memory_map):
     assert _compare(tmp_path, "bias_finetuning", skip_suffix=".bias", layer_filter="TransformerLayer") > 0
 
 
-@needs_fixtures
 @pytest.mark.parametrize("mp,pp,world", [(1, 1, 1), (2, 1, 2)])
 def test_finetuning_with_ignore_keys_in_checkpoint(tmp_path, mp, pp, world):
     cfg = _config(tmp_path, mp, pp, world, acc=2)
@@ -159,7 +152,6 @@ def test_finetuning_with_ignore_keys_in_checkpoint(tmp_path, mp, pp, world):
     assert len(losses) == 4 and all(np.isfinite(m["training/loss"]) for m in losses)
 
 
-@needs_fixtures
 @pytest.mark.parametrize("mp,pp,world", [(1, 1, 1), (1, 2, 2)])
 @pytest.mark.parametrize("finetunable", [["embedding.weight"], ["embedding.weight", "mlp.dense_in.weight"]])
 @pytest.mark.parametrize("tied", [True, False])

@@ -10,11 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests.golden_files import FILES
 from tests.test_training import _config, _make_data, _run
 
 pytestmark = pytest.mark.cpu
-FILES = Path("/root/reference/tests/transformer/files")
-needs_fixtures = pytest.mark.skipif(not (FILES / "dataset" / "data.bin").exists(), reason="reference fixtures not mounted")
 
 
 def _losses(ms):
@@ -130,7 +129,6 @@ def test_local_attention_training(tmp_path, mp, pp, world, local_heads):
     assert _losses(resumed) == _losses(full)[-4:]
 
 
-@needs_fixtures
 @pytest.mark.parametrize("mp,pp,world", [(1, 1, 1), (1, 2, 2)])
 def test_legacy_dataset_training(tmp_path, mp, pp, world):
     """Reference test_training_legacy.py: training on the Megatron MMIDIDX (Enron) fixture, blended x2."""
@@ -144,7 +142,6 @@ def test_legacy_dataset_training(tmp_path, mp, pp, world):
     assert _losses(resumed) == _losses(full)[-4:]
 
 
-@needs_fixtures
 @pytest.mark.parametrize("mp,pp,world", [(1, 1, 1), (2, 1, 2)])
 def test_chat_finetuning_softprompt(tmp_path, mp, pp, world):
     """Reference test_training_finetuning_chat.py: pretrain on chat data, then finetune a softprompt only."""
