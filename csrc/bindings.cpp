@@ -730,9 +730,42 @@ at::Tensor dropout_add(const at::Tensor& x_, const c10::optional<at::Tensor>& re
                            (uint32_t)seed, drop_threshold(p), (float)(1.0 / (1.0 - p)), cur_stream());
     return out;
 }
+
+// ------------------------------------------------------------------ sampling
+// tokens [B] int64 (and info [B, 2] int32 when asked) for logits [B, V] with unit last stride; step: one int64 on the GPU
+std::vector<at::Tensor> sample_logits(const at::Tensor& logits, const at::Tensor& step, int64_t seed, double temperature,
+                                      int64_t top_k, double top_p, bool want_info) {
+    TORCH_CHECK(logits.is_cuda() && logits.dim() == 2, "sample: logits must be a [B, V] GPU tensor");
+    const int64_t B = logits.size(0), V = logits.size(1);
+    TORCH_CHECK(V >= 1 && V <= (1 << 22), "sample: vocabulary size must be in [1, 2^22]");
+    TORCH_CHECK(B <= INT32_MAX, "sample: too many rows");
+    TORCH_CHECK(logits.stride(1) == 1 || V == 1, "sample: logits need a unit last stride");
+    TORCH_CHECK(B <= 1 || logits.stride(0) >= 0, "sample: negative row stride");
+    TORCH_CHECK(step.is_cuda() && step.scalar_type() == at::kLong && step.numel() == 1 &&
+                step.device() == logits.device(), "sample: step must be one int64 on the logits' device");
+    TORCH_CHECK(temperature > 0.0 && std::isfinite(temperature), "sample: temperature must be positive");
+    TORCH_CHECK(!std::isnan(top_p), "sample: top_p is NaN");
+    const int code = dt(logits);
+    const at::DeviceGuard g(logits.device());
+    auto tokens = at::empty({B}, logits.options().dtype(at::kLong));
+    at::Tensor info;
+    if (want_info) info = at::empty({B, 2}, logits.options().dtype(at::kInt));
+    if (B > 0)
+        sa_launch::sample(code, logits.data_ptr(), B > 1 ? logits.stride(0) : 0, B, (int)V, tokens.data_ptr<int64_t>(),
+                          want_info ? info.data_ptr<int>() : nullptr, step.data_ptr<int64_t>(), (uint32_t)seed,
+                          (int)std::max<int64_t>(0, std::min<int64_t>(top_k, V)), (float)std::max(top_p, 0.0),
+                          (float)temperature, cur_stream());
+    if (want_info) return {tokens, info};
+    return {tokens};
+}
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+    m.def("sample_logits", &sample_logits, "one draw per row of logits [B, V] after top-k / top-p / temperature "
+          "(graph-safe: the step is read on the device)", py::arg("logits"), py::arg("step"), py::arg("seed"),
+          py::arg("temperature"), py::arg("top_k"), py::arg("top_p"), py::arg("want_info") = false);
+    m.def("sample_max_resident_vocab", []() { return sa_launch::sample_max_resident(); },
+          "the largest vocabulary whose row the sampling kernel stages in LDS");
     m.doc() = "scaling_amd CDNA4 (gfx950) HIP kernels";
     register_rehearsal(m);
     register_blaslt(m);

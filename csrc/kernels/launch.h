@@ -145,6 +145,14 @@ void oneshot_allreduce(int dtype, char* const* bases, int world, int rank, int64
                        hipStream_t st);
 }
 
+namespace sa_launch {
+// sample.hip: tokens[b] = one draw from top-k / top-p / temperature-filtered logits[b, :] (row stride ld, unit last
+// stride); the uniform is a hash of (seed, *step, b); info (may be null) [B, 2] int32: kept count, bits of the cut logit
+int sample_max_resident();  // the largest V whose row is staged in LDS
+void sample(int dtype, const void* logits, int64_t ld, int64_t B, int V, int64_t* tokens, int* info,
+            const int64_t* step, uint32_t seed, int top_k, float top_p, float temperature, hipStream_t st);
+}  // namespace sa_launch
+
 // gemv.hip epi 3: interleaved RoPE of q / k and the K/V cache append at the device-side position
 struct GemvRope {
     const float* cosb; const float* sinb; const int64_t* pos;

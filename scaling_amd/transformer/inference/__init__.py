@@ -1,8 +1,9 @@
 from .inference_model import CompletionOutput, TransformerInferenceModule
-from .sample import fast_multinomial, sample_argmax, sample_temperature, top_k_transform, top_p_transform
+from .sample import Sampler, fast_multinomial, sample_argmax, sample_temperature, top_k_transform, top_p_transform
 
 __all__ = [
     "CompletionOutput",
+    "Sampler",
     "TransformerInferenceModule",
     "fast_multinomial",
     "sample_argmax",

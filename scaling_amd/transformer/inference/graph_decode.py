@@ -13,8 +13,11 @@ fixed capacity, so it is captured once and replayed:
   device-side step index and advances the position — the host only replays and, every ``check_every`` steps,
   reads the tokens back to honour stop tokens.
 
-Sampling must be graph-safe (device ops, no host sync): ``sample_argmax`` is; samplers that draw random numbers
-are not supported here (they would replay the same draws).
+Sampling must be graph-safe (device ops, no host sync): ``sample_argmax`` is, and so is ``sample.Sampler`` (fused
+top-k / top-p / temperature, one launch): its random draw is a hash of (seed, step, row) with the step read from a
+device counter that the captured step itself advances, so every replay draws a fresh number and the tokens equal
+the eager loop's.  Samplers that draw with ``torch.rand`` (``sample_temperature``: not a replay-safe draw) or index
+with a boolean mask (``top_p_transform``: a host sync) cannot be captured.
 """
 from __future__ import annotations
 
@@ -85,6 +88,8 @@ class GraphDecoder:
     def _rewind(self) -> None:
         self.state.reset(self.n_prompt)
         self.tok.copy_(self.first)
+        if hasattr(self.sample_fn, "reset"):
+            self.sample_fn.reset(1)  # step 0 drew the prefill's token; the warm-up and capture passes burn no draws
 
     def run(self, stop_tokens: Sequence[int], check_every: int = 8) -> tuple[list[int], torch.Tensor]:
         """Replays steps 1 .. max_tokens-1 (step 0 is the prefill's token); returns tokens (through the first

@@ -96,13 +96,15 @@ class TransformerInferenceModule(InferenceModule):
         """Completion text / tokens / logits for a prompt.  With the KV cache each step feeds only the new
         token (with its absolute position); without it the whole sequence is re-run.
 
-        ``use_cuda_graph`` (KV cache, one GPU, flash attention, a graph-safe sampler such as ``sample_argmax``):
-        after the prefill, the decode step is captured once as a HIP graph and replayed per token
+        ``use_cuda_graph`` (KV cache, one GPU, flash attention, a graph-safe sampler: ``sample_argmax`` or
+        ``sample.Sampler``): after the prefill, the decode step is captured once as a HIP graph and replayed per token
         (``graph_decode.GraphDecoder``) — same kernels and results as the eager loop, without its per-token
         launch and Python overhead."""
         if stop_tokens is None:
             assert self.tokenizer is not None, "If no tokenizer is provided, a stop token needs to be set manually"
             stop_tokens = [self.tokenizer.eos_token_id]
+        if hasattr(sample_fn, "reset"):
+            sample_fn.reset(0)  # a seeded sampler (``sample.Sampler``) repeats its text from one call to the next
         cur = self._pre_process_input(input_text, input_tokens, process_for_cached_inference=use_cache)
         assert cur.input_token_ids is not None
         n_in = cur.input_token_ids.shape[-1]

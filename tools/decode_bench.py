@@ -1,6 +1,10 @@
-"""Batch-1 greedy decode latency on one GPU: eager cached generation vs HIP-graph-captured decoding.
+"""Batch-1 decode latency on one GPU: eager cached generation vs HIP-graph-captured decoding, greedy or sampled.
 
-    python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64]
+    python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64] [--sampler T,K,P | torch:T,K,P]
+
+``--sampler 0.8,40,0.95`` decodes with the fused ``Sampler`` (temperature, top-k, top-p) in both loops;
+``--sampler torch:0.8,40,0.95`` times the eager loop with the torch composition
+``sample_temperature(top_p_transform(top_k_transform(x, k), p), T)``, which cannot be captured (no graph figures).
 
 Random-init weights of the named preset; the prompt is random token ids.  Per-token time excludes the prefill
 (eager: generate(N+1) - generate(1); graph: the replay loop alone, capture reported separately).  Prints one
@@ -25,10 +29,12 @@ def main() -> None:
     p.add_argument("--prompt", type=int, default=128)
     p.add_argument("--tokens", type=int, default=64)
     p.add_argument("--num-layers", type=int, default=None)
+    p.add_argument("--sampler", default=None, help="T,K,P: fused Sampler; torch:T,K,P: torch composition (eager only)")
     a = p.parse_args()
     from scaling_amd.models import llama_architecture
     from scaling_amd.transformer.context.config import TransformerArchitectureConfig
-    from scaling_amd.transformer.inference import TransformerInferenceModule, sample_argmax
+    from scaling_amd.transformer.inference import (Sampler, TransformerInferenceModule, sample_argmax, sample_temperature,
+                                                   top_k_transform, top_p_transform)
     from scaling_amd.transformer.inference.graph_decode import GraphDecoder
     from scaling_amd.transformer.model.model import get_transformer_layer_specs
     from scaling_amd.utils.gemm_tuning import enable_tuned_gemms
@@ -42,6 +48,19 @@ def main() -> None:
     m = TransformerInferenceModule(get_transformer_layer_specs(arch), devices=(0,))
     prompt = torch.randint(1, arch.vocab_size, (a.prompt,)).tolist()
 
+    sample_fn, graph_ok, mode = sample_argmax, True, "greedy"
+    if a.sampler:
+        spec = a.sampler.split(":")[-1].split(",")
+        temp, top_k, top_p = float(spec[0]), int(spec[1]), float(spec[2])
+        if a.sampler.startswith("torch:"):
+            def sample_fn(x):
+                return sample_temperature(top_p_transform(top_k_transform(x[0, -1], top_k), top_p)[None, None], temp)
+            graph_ok, mode = False, f"torch composition T={temp} k={top_k} p={top_p}"
+        else:
+            sample_fn, mode = Sampler(temp, top_k, top_p, seed=0), f"fused sampler T={temp} k={top_k} p={top_p}"
+
+    metric = "batch-1 greedy decode ms/token" if mode == "greedy" else "batch-1 sampled decode ms/token"
+
     def timed(fn):
         torch.cuda.synchronize()
         t = time.perf_counter()
@@ -49,25 +68,35 @@ def main() -> None:
         torch.cuda.synchronize()
         return time.perf_counter() - t, r
 
-    m.generate(4, input_tokens=prompt, stop_tokens=[])  # warm-up (library handles, tables)
-    t1, _ = timed(lambda: m.generate(1, input_tokens=prompt, stop_tokens=[]))
-    tn, eager = timed(lambda: m.generate(a.tokens + 1, input_tokens=prompt, stop_tokens=[]))
+    m.generate(4, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn)  # warm-up (library handles, tables)
+    t1, _ = timed(lambda: m.generate(1, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn))
+    tn, eager = timed(lambda: m.generate(a.tokens + 1, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn))
     eager_ms = 1000.0 * (tn - t1) / a.tokens
+    weights = sum(p.numel() * p.element_size() for p in m.parameters())
+    if not graph_ok:
+        print(json.dumps({
+            "metric": metric, "sampler": mode, "model": a.model, "layers": arch.num_layers,
+            "prompt": a.prompt, "tokens": a.tokens, "eager_ms_per_token": round(eager_ms, 3),
+            "weights_gib": round(weights / 2**30, 2),
+        }), flush=True)
+        return
 
+    if hasattr(sample_fn, "reset"):
+        sample_fn.reset(0)
     cur = m._pre_process_input(None, prompt, True)
     out = m.forward(cur)
-    first = sample_argmax(out.activations)
-    dec = GraphDecoder(m, a.prompt, a.tokens + 1, first, sample_argmax, out.activations[:, -1, :])
+    first = sample_fn(out.activations)
+    dec = GraphDecoder(m, a.prompt, a.tokens + 1, first, sample_fn, out.activations[:, -1, :])
     tc, _ = timed(dec.capture)
     tg, (toks, _) = timed(lambda: dec.run([], check_every=a.tokens + 1))
     graph_ms = 1000.0 * tg / a.tokens
     same = toks == eager.completion_tokens
     print(json.dumps({
-        "metric": "batch-1 greedy decode ms/token", "model": a.model, "layers": arch.num_layers, "prompt": a.prompt,
+        "metric": metric, "sampler": mode, "model": a.model, "layers": arch.num_layers, "prompt": a.prompt,
         "tokens": a.tokens, "eager_ms_per_token": round(eager_ms, 3), "graph_ms_per_token": round(graph_ms, 3),
         "speedup": round(eager_ms / graph_ms, 2), "graph_capture_ms": round(1000.0 * tc, 1),
-        "graph_tokens_equal_eager": same, "weights_gib": round(sum(p.numel() * p.element_size() for p in m.parameters()) / 2**30, 2),
-        "graph_gb_per_s": round(sum(p.numel() * p.element_size() for p in m.parameters()) / (graph_ms * 1e-3) / 1e9, 1),
+        "graph_tokens_equal_eager": same, "weights_gib": round(weights / 2**30, 2),
+        "graph_gb_per_s": round(weights / (graph_ms * 1e-3) / 1e9, 1),
     }), flush=True)
 
 
