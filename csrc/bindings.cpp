@@ -445,6 +445,89 @@ c10::optional<at::Tensor> gemv_norm_rope(const at::Tensor& x, const at::Tensor& 
     return q;
 }
 
+// ------------------------------------------------------------------ GEMV over FP8 weights (gemv_fp8.hip)
+// W = scale[n] * Q[n, :]: Q [N, K] OCP e4m3fn codes (float8_e4m3fn, or the same bytes as uint8), scale [N] fp32
+// powers of two (ops/quant.py); x bf16 [M <= 4, K].  16-byte pieces of 16 codes: K % 16 == 0, Q rows a multiple of
+// 16 bytes apart, 16-byte aligned bases.
+bool gemv_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    if (!(x.is_cuda() && Q.is_cuda() && scale.is_cuda() && x.dim() == 2 && Q.dim() == 2 && scale.dim() == 1)) return false;
+    if (Q.device() != x.device() || scale.device() != x.device()) return false;
+    if (x.scalar_type() != at::kBFloat16 || (Q.scalar_type() != at::kFloat8_e4m3fn && Q.scalar_type() != at::kByte))
+        return false;
+    if (scale.scalar_type() != at::kFloat || scale.numel() != Q.size(0) || !scale.is_contiguous()) return false;
+    if (x.size(0) < 1 || x.size(0) > 4 || x.size(1) != Q.size(1) || x.size(1) % 16 != 0 || x.size(1) < 16 || Q.size(0) < 1)
+        return false;
+    if (x.stride(1) != 1 || Q.stride(1) != 1 || (x.size(0) > 1 && x.stride(0) % 8 != 0) || Q.stride(0) % 16 != 0 ||
+        Q.stride(0) < Q.size(1))
+        return false;
+    return (uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)Q.data_ptr() % 16 == 0 && (uintptr_t)scale.data_ptr() % 4 == 0;
+}
+at::Tensor gemv_w8(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, c10::optional<at::Tensor> bias) {
+    TORCH_CHECK(gemv_w8_ok(x, Q, scale), "gemv_w8: unsupported operands (x bf16 [M<=4, K], Q e4m3fn [N, K], scale fp32 "
+                                         "[N], K % 16 == 0, 16-byte aligned rows)");
+    const at::DeviceGuard g(x.device());
+    const int64_t M = x.size(0), N = Q.size(0), K = Q.size(1);
+    const void* bp = nullptr;
+    at::Tensor bc;
+    if (bias.has_value() && bias->defined()) {
+        TORCH_CHECK(bias->is_cuda() && bias->numel() == N && bias->scalar_type() == x.scalar_type(), "gemv_w8: bias");
+        bc = bias->contiguous();
+        bp = bc.data_ptr();
+    }
+    auto y = at::empty({M, N}, x.options());
+    sa_launch::gemv_w8((int)M, x.data_ptr(), x.stride(0), Q.data_ptr(), Q.stride(0), scale.data_ptr<float>(), bp,
+                       y.data_ptr(), N, (int)N, (int)K, cur_stream());
+    return y;
+}
+at::Tensor gemv_w8_residual(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& res) {
+    TORCH_CHECK(gemv_w8_ok(x, Q, scale), "gemv_w8_residual: unsupported operands");
+    const int64_t M = x.size(0), N = Q.size(0), K = Q.size(1);
+    TORCH_CHECK(res.is_cuda() && res.dim() == 2 && res.size(0) == M && res.size(1) == N && res.stride(1) == 1 &&
+                    res.scalar_type() == x.scalar_type(), "gemv_w8_residual: res must be [M, N] of the input dtype");
+    const at::DeviceGuard g(x.device());
+    auto y = at::empty({M, N}, x.options());
+    sa_launch::gemv_w8((int)M, x.data_ptr(), x.stride(0), Q.data_ptr(), Q.stride(0), scale.data_ptr<float>(), nullptr,
+                       y.data_ptr(), N, (int)N, (int)K, cur_stream(), 1, res.data_ptr(), res.stride(0));
+    return y;
+}
+// SwiGLU over Q = [gate; up] ([2F, K], scale [2F]: the halves keep their own row scales)
+at::Tensor gemv_w8_swiglu(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    TORCH_CHECK(gemv_w8_ok(x, Q, scale) && Q.size(0) % 2 == 0, "gemv_w8_swiglu: unsupported operands");
+    const int64_t M = x.size(0), F = Q.size(0) / 2, K = Q.size(1);
+    const at::DeviceGuard g(x.device());
+    auto y = at::empty({M, F}, x.options());
+    sa_launch::gemv_w8((int)M, x.data_ptr(), x.stride(0), Q.data_ptr(), Q.stride(0), scale.data_ptr<float>(), nullptr,
+                       y.data_ptr(), F, (int)F, (int)K, cur_stream(), 2, nullptr, 0);
+    return y;
+}
+bool gemv_w8_norm_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& gamma) {
+    if (!gemv_w8_ok(x, Q, scale) || !x.is_contiguous()) return false;
+    return gamma.is_cuda() && gamma.dim() == 1 && gamma.numel() == x.size(1) && gamma.is_contiguous() &&
+           gamma.scalar_type() == x.scalar_type() && (uintptr_t)gamma.data_ptr() % 16 == 0;
+}
+// (s, y) as gemv_norm: s = x (+ add); y = gemv_w8(rms_norm(s, gamma, eps), Q, scale), epi 0 plain or 2 SwiGLU
+std::vector<at::Tensor> gemv_w8_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
+                                     double eps, const at::Tensor& Q, const at::Tensor& scale, int64_t epi) {
+    TORCH_CHECK(gemv_w8_norm_ok(x, Q, scale, gamma) && (epi == 0 || (epi == 2 && Q.size(0) % 2 == 0)),
+                "gemv_w8_norm: unsupported operands");
+    const int64_t M = x.size(0), K = Q.size(1), N = epi == 2 ? Q.size(0) / 2 : Q.size(0);
+    const at::DeviceGuard g(x.device());
+    at::Tensor s = x;
+    const void* ap = nullptr;
+    if (add.has_value() && add->defined()) {
+        TORCH_CHECK(add->is_cuda() && add->sizes() == x.sizes() && add->is_contiguous() &&
+                        add->scalar_type() == x.scalar_type() && (uintptr_t)add->data_ptr() % 16 == 0,
+                    "gemv_w8_norm: add must be a contiguous, aligned [M, K]");
+        s = at::empty_like(x);
+        ap = add->data_ptr();
+    }
+    auto y = at::empty({M, N}, x.options());
+    sa_launch::gemv_w8((int)M, x.data_ptr(), x.stride(0), Q.data_ptr(), Q.stride(0), scale.data_ptr<float>(), nullptr,
+                       y.data_ptr(), N, (int)N, (int)K, cur_stream(), (int)epi, nullptr, 0, gamma.data_ptr(), ap,
+                       ap ? s.data_ptr() : nullptr, (float)eps);
+    return {s, y};
+}
+
 // ------------------------------------------------------------------ GEMM (weight gradient)
 // C[M, N] = A^T B (+ C if accumulate); A: [K, M], B: [K, N], C: [M, N], bf16, unit inner strides.
 bool gemm_tn_ok(const at::Tensor& A, const at::Tensor& B, const at::Tensor& C) {
@@ -786,6 +869,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemv", &gemv, "y = x W^T (+ b) for at most 4 rows of x (decode-time linear layers)", py::arg("x"), py::arg("W"), py::arg("bias") = py::none());
     m.def("gemv_residual", &gemv_residual, "y = x W^T + res for at most 4 rows (decode MLP-out + residual)");
     m.def("gemv_swiglu", &gemv_swiglu, "y = silu(x Wg^T) * (x Wu^T) for W = [Wg; Wu], at most 4 rows (decode)");
+    m.def("gemv_w8_ok", &gemv_w8_ok, "whether the FP8-weight GEMV supports these operands");
+    m.def("gemv_w8", &gemv_w8, "y = x (scale * Q)^T (+ b) for at most 4 bf16 rows of x, Q e4m3fn codes, scale fp32 per row",
+          py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("bias") = py::none());
+    m.def("gemv_w8_residual", &gemv_w8_residual, "gemv_w8 + res (decode down / o-projection + residual)");
+    m.def("gemv_w8_swiglu", &gemv_w8_swiglu, "silu(x Wg^T) * (x Wu^T) over FP8 [Wg; Wu] with per-row scales (decode)");
+    m.def("gemv_w8_norm_ok", &gemv_w8_norm_ok, "whether gemv_w8_norm supports these operands");
+    m.def("gemv_w8_norm", &gemv_w8_norm, "(s, gemv_w8(rms_norm(s), Q, scale)) with s = x (+ add); epi 0 plain, 2 SwiGLU",
+          py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("q"), py::arg("scale"), py::arg("epi") = 0);
     m.def("gemv_norm_ok", &gemv_norm_ok, "whether gemv_norm supports these operands");
     m.def("gemv_norm_rope", &gemv_norm_rope, "graph decode: rms_norm + q/k/v GEMV + interleaved RoPE + K/V cache append "
           "in one launch; returns q or None");

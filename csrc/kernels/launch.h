@@ -166,4 +166,9 @@ void gemv(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t l
           int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
           const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
           const struct GemvRope* rope = nullptr);
+// gemv_fp8.hip: the same layer over FP8 weights W = scale[n] * Q[n, :] (Q OCP e4m3fn codes, rows ldq bytes apart,
+// scale one fp32 power of two per code row), x / b / res / y / norm_* bf16, K % 16 == 0; epi 0 / 1 / 2 as gemv()
+void gemv_w8(int M, const void* x, int64_t ldx, const void* Q, int64_t ldq, const float* scale, const void* b, void* y,
+             int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
+             const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f);
 }  // namespace sa_launch

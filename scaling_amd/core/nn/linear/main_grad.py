@@ -51,7 +51,8 @@ import torch.distributed as dist
 
 from ....ops.attention import stash_gemm
 from ....ops.gemm import linear as gemm_linear
-from ....ops.gemm import mm, mm_nt, transpose2d, wgrad
+from ....ops.gemm import GEMV_MAX_ROWS, mm, mm_nt, transpose2d, wgrad
+from ....ops.quant import adjacent_w8 as _adjacent_w8
 from ...utils.debug_env import side_streams_enabled
 
 _GEN = [0]
@@ -172,6 +173,13 @@ def adjacent_weights(weights: Sequence[torch.Tensor]) -> Optional[torch.Tensor]:
     return w
 
 
+def adjacent_w8(weights: Sequence[torch.Tensor]) -> Optional[tuple[torch.Tensor, torch.Tensor]]:
+    """The fused FP8 copy ``(q [sum N, K], scale [sum N])`` of weights quantised as one group (``ops/quant.py``:
+    the members' copies are row slices of one buffer), mirroring ``_adjacent``; None without a valid copy of every
+    member (a stale copy is dropped there, with a warning)."""
+    return _adjacent_w8(weights)
+
+
 def _main_grad_target(weights: Sequence[torch.Tensor]) -> Optional[torch.Tensor]:
     if not all(getattr(w, "_sa_main_grad", False) and w.grad is not None for w in weights):
         return None
@@ -235,7 +243,10 @@ class _MultiLinear(torch.autograd.Function):
         b = None
         if has_bias:
             b = biases[0] if n == 1 else torch.cat(biases, dim=0)  # type: ignore[arg-type]
-        out = stash_gemm(lambda: gemm_linear(x, w, b))
+        # decode-sized rows of quantised weights stream the FP8 copy (w itself may be a fresh view over the group)
+        K = x.shape[-1]
+        w8 = adjacent_w8(weights) if K and 0 < x.numel() // K <= GEMV_MAX_ROWS else None  # type: ignore[arg-type]
+        out = stash_gemm(lambda: gemm_linear(x, w, b, w8=w8))
         wt = _transposed(weights, w) if want_wt else None
         ctx.has_wt = wt is not None
         ctx.save_for_backward(x, wt if wt is not None else w, *weights)

@@ -22,7 +22,7 @@ from .activation_function import ActivationFunction, get_activation_function
 from .linear import ColumnParallelLinear, RowParallelLinear
 from .linear.fused import fused_column_linear
 from .linear.tp_overlap import sp_gather_column
-from .linear.main_grad import adjacent_weights
+from .linear.main_grad import adjacent_w8, adjacent_weights
 
 
 def _intermediate(io_features: int, factor: float) -> int:
@@ -115,6 +115,17 @@ class ParallelSwiGLUMLP(torch.nn.Module):
             return None
         return w, wo
 
+    def _decode_w8(self) -> tuple[Optional[tuple], Optional[tuple]]:
+        """The valid FP8 copies ``(q, scale)`` of ``[gate; up]`` and of the down projection (``ops/quant.py``), each
+        None without one: that GEMV then streams the bf16 weight as before."""
+        return adjacent_w8([self.dense_in.weight, self.siglu_weight.weight]), adjacent_w8([self.dense_out.weight])
+
+    @staticmethod
+    def _down_residual(a: torch.Tensor, wo: torch.Tensor, wo8: Optional[tuple], res: torch.Tensor) -> torch.Tensor:
+        if wo8 is not None and ext().gemv_w8_ok(a, wo8[0], wo8[1]):
+            return ext().gemv_w8_residual(a, wo8[0], wo8[1], res)
+        return ext().gemv_residual(a, wo, res)
+
     def decode_forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> Optional[torch.Tensor]:
         """``residual + self(x)`` for decode-sized inputs (<= 4 tokens, no autograd graph, TP 1, bias-free) as two
         GEMV launches with fused epilogues -- gate/up GEMV + SwiGLU, down GEMV + residual add -- bit-identical to
@@ -123,8 +134,13 @@ class ParallelSwiGLUMLP(torch.nn.Module):
         if ws is None:
             return None
         rows = x.numel() // x.shape[-1]
-        h = ext().gemv_swiglu(x.reshape(rows, -1), ws[0])
-        return ext().gemv_residual(h, ws[1], residual.reshape(rows, -1)).view(residual.shape)
+        x2 = x.reshape(rows, -1)
+        w8, wo8 = self._decode_w8()
+        if w8 is not None and ext().gemv_w8_ok(x2, w8[0], w8[1]):
+            h = ext().gemv_w8_swiglu(x2, w8[0], w8[1])
+        else:
+            h = ext().gemv_swiglu(x2, ws[0])
+        return self._down_residual(h, ws[1], wo8, residual.reshape(rows, -1)).view(residual.shape)
 
     def decode_forward_norm(self, h: torch.Tensor, residual: torch.Tensor, norm: torch.nn.Module) -> Optional[torch.Tensor]:
         """``s + self(norm(s))`` with ``s = residual + h`` (the post-attention residual add, RMSNorm and MLP of a
@@ -144,8 +160,12 @@ class ParallelSwiGLUMLP(torch.nn.Module):
         h2 = h.reshape(rows, -1)
         if not ext().gemv_norm_ok(h2, ws[0], nw[0]):
             return None
-        s, a = ext().gemv_norm(h2, residual.reshape(rows, -1), nw[0], nw[1], ws[0], 2)
-        return ext().gemv_residual(a, ws[1], s).view(residual.shape)
+        w8, wo8 = self._decode_w8()
+        if w8 is not None and ext().gemv_w8_norm_ok(h2, w8[0], w8[1], nw[0]):
+            s, a = ext().gemv_w8_norm(h2, residual.reshape(rows, -1), nw[0], nw[1], w8[0], w8[1], 2)
+        else:
+            s, a = ext().gemv_norm(h2, residual.reshape(rows, -1), nw[0], nw[1], ws[0], 2)
+        return self._down_residual(a, ws[1], wo8, s).view(residual.shape)
 
     def forward(self, x: torch.Tensor, sp_shard: bool = False) -> torch.Tensor:
         """``sp_shard``: ``x`` is this rank's sequence-parallel token shard; its gather runs folded into (and overlapped

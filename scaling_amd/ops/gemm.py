@@ -13,7 +13,8 @@ round 5).  Shapes it does not tile (M/N not multiples of 16, T not a multiple of
 
 ``linear`` is the forward ``x W^T (+ b)`` of every linear layer, ``mm_nt`` the input gradient ``dY (W^T)^T`` on
 the cached transpose and ``mm`` the input gradient ``dY W`` without it: at most 4 token rows (token-by-token decoding)
-run the weight-streaming GEMV kernel (``csrc/kernels/gemv.hip``); small products (<= ``SCALING_AMD_LT_SMALL_FLOP``
+run the weight-streaming GEMV kernel (``csrc/kernels/gemv.hip``; ``gemv_fp8.hip`` for a weight that carries a valid
+FP8 copy, ``ops/quant.py``); small products (<= ``SCALING_AMD_LT_SMALL_FLOP``
 multiply-adds, 2^33 by default: none of the 7B step's) go through cached hipBLASLt plans (``csrc/blaslt.cpp``); the
 rest are plain library GEMMs (hipBLASLt through torch, TunableOp table ``scaling_amd/tuning/gemm_gfx950.csv``).  A hand-written NT GEMM with fused SwiGLU epilogues (rounds 3-5) stayed
 1-6 % behind hipBLASLt at every 7B shape and lost in the step even with its epilogues
@@ -27,6 +28,7 @@ from typing import Optional
 import torch
 
 from ._ext import ext, use_native
+from .quant import w8_of
 
 
 _WGRAD_RAGGED = os.environ.get("SCALING_AMD_WGRAD_RAGGED", "1") != "0"
@@ -88,16 +90,25 @@ def mm_nt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.matmul(a, b.t())
 
 
-def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
+           w8: Optional[tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """``F.linear(x, w, b)``; decode-sized inputs (<= 4 rows) on the GEMV kernel.
 
     The GEMV kernel is a raw op without autograd, so it only serves calls that build no graph (grad mode off, or
-    no operand requiring grad); a tiny training micro-batch through a tied head keeps ``F.linear``'s backward."""
+    no operand requiring grad); a tiny training micro-batch through a tied head keeps ``F.linear``'s backward.
+
+    A weight quantised by ``ops.quant`` (``w8``: its valid FP8 copy ``(q, scale)``, looked up on ``w`` when not
+    given) streams the copy through the FP8 GEMV (``csrc/kernels/gemv_fp8.hip``) on that same branch; ``w`` holds
+    the dequantised values, so every other branch computes the same function."""
     K = x.shape[-1]
     rows = x.numel() // K if K else 0
     needs_graph = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad))
+    if w8 is None and getattr(w, "_sa_w8", None) is not None:
+        w8 = w8_of(w)  # (drops a stale copy, whichever branch serves this call)
     if 0 < rows <= GEMV_MAX_ROWS and not needs_graph and use_native(x) and w.dim() == 2:
         x2 = x.reshape(rows, K)
+        if w8 is not None and ext().gemv_w8_ok(x2, w8[0], w8[1]) and (b is None or b.dtype == x.dtype):
+            return ext().gemv_w8(x2, w8[0], w8[1], b).reshape(*x.shape[:-1], w.shape[0])
         if ext().gemv_ok(x2, w) and (b is None or b.dtype == w.dtype):
             return ext().gemv(x2, w, b).reshape(*x.shape[:-1], w.shape[0])
     if not needs_graph and w.dim() == 2 and _lt_ok(x, w, rows, w.shape[0], K) and (b is None or b.dtype == w.dtype):

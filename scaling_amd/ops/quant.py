@@ -1,0 +1,132 @@
+"""FP8 weight-only quantisation for token-by-token decoding (``csrc/kernels/gemv_fp8.hip``).
+
+Scheme ``fp8_e4m3``: one output row of ``W [N, K]`` at a time.
+
+* codes: OCP ``e4m3fn`` (``torch.float8_e4m3fn``; not the ``fnuz`` variant), one byte per weight;
+* scale: one fp32 **power of two** per row, ``s = 2^ceil(log2(amax / 448))`` so that ``amax / s`` lies in
+  ``(224, 448]`` (``s = 1`` for an all-zero row);
+* ``q = cast_e4m3(clamp(w / s, -448, 448))``, round to nearest even in fp32; the NaN codes are never produced and
+  non-finite input is refused.
+
+Because the scale is a power of two, ``q * s`` is exactly representable in bf16 (a code has 4 significant bits, bf16
+has 8): the FP8 copy is an exact encoding of a bf16 matrix.  ``quantize_parameters`` therefore overwrites the bf16
+parameter with the dequantised values, and every path that does not stream the FP8 copy -- prefill GEMMs, CPU, any
+fallback -- computes the same function from the same weights.
+
+The copy hangs on the parameter as ``_sa_w8 = (q, scale, version)``; ``version`` is the parameter's ``_version`` right
+after the dequantised values were written back.  Any later in-place change of the parameter (checkpoint load,
+optimizer step, LoRA merge) moves ``_version``: the copy is then dropped with a one-time warning and the bf16 path
+serves the layer.  A stale copy is never used.
+"""
+from __future__ import annotations
+
+import warnings
+from typing import Optional, Sequence
+
+import torch
+
+FP8_MAX = 448.0
+SCHEME = "fp8_e4m3"
+PIECE = 16  # weights per 16-byte piece of the GEMV kernel: K must be a multiple
+_ATTR = "_sa_w8"
+_MIN_EXP = -100  # smallest row-scale exponent: q * s stays a normal bf16 / fp32 number down to the subnormal codes
+_warned = [False]
+
+
+def quantize_rows_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``(q [N, K] float8_e4m3fn, scale [N] fp32)`` of a 2-D matrix, one power-of-two scale per row."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_rows_fp8: expected a 2-D weight, got shape {tuple(w.shape)}")
+    wf = w.detach().float()
+    if not bool(torch.isfinite(wf).all()):
+        raise ValueError("quantize_rows_fp8: the weight holds non-finite values")
+    amax = wf.abs().amax(dim=1) if wf.shape[1] > 0 else wf.new_zeros(wf.shape[0])
+    zero = amax == 0
+    # amax / 448 = m * 2^e with m in [0.5, 1): ceil(log2) is e, or e - 1 when m is exactly 0.5
+    m, e = torch.frexp(torch.where(zero, torch.full_like(amax, FP8_MAX), amax) / FP8_MAX)
+    e = torch.where(m == 0.5, e - 1, e).clamp_(min=_MIN_EXP)
+    one = torch.ones_like(amax)
+    s = torch.ldexp(one, e)
+    # guard the rounding of the division: amax <= 448 s must hold, and must fail for s / 2 (both products are exact)
+    s = torch.where(amax > FP8_MAX * s, s * 2, s)
+    s = torch.where((amax <= (FP8_MAX / 2) * s) & (torch.ldexp(one, torch.full_like(e, _MIN_EXP)) < s), s / 2, s)
+    s = torch.where(zero, one, s)
+    q = (wf / s[:, None]).clamp_(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return q, s
+
+
+def dequantize_rows_fp8(q: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """``q * scale[:, None]`` in ``dtype`` (exact in bf16 and fp32 for the scales ``quantize_rows_fp8`` makes)."""
+    if q.dtype == torch.uint8:
+        q = q.view(torch.float8_e4m3fn)
+    return (q.float() * scale.float()[:, None]).to(dtype)
+
+
+def attach_w8(param: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> None:
+    """Hangs the FP8 copy on ``param``; call right after the dequantised values were written into it."""
+    setattr(param, _ATTR, (q, scale, param._version))
+
+
+def drop_w8(param: torch.Tensor) -> None:
+    if hasattr(param, _ATTR):
+        delattr(param, _ATTR)
+
+
+def w8_of(param: torch.Tensor) -> Optional[tuple[torch.Tensor, torch.Tensor]]:
+    """The valid FP8 copy ``(q, scale)`` of ``param``, or None.  A copy whose parameter changed in place since it
+    was made is dropped (one warning per process) and None is returned: the caller takes the bf16 path."""
+    c = getattr(param, _ATTR, None)
+    if c is None:
+        return None
+    if c[2] != param._version or c[0].shape != param.shape or c[0].device != param.device:
+        delattr(param, _ATTR)
+        if not _warned[0]:
+            _warned[0] = True
+            warnings.warn("scaling_amd: a quantised weight was modified after quantize_weights(); its FP8 copy is "
+                          "dropped and the layer runs from the bf16 parameter (call quantize_weights() again to "
+                          "re-quantise)", RuntimeWarning, stacklevel=2)
+        return None
+    return c[0], c[1]
+
+
+def adjacent_w8(weights: Sequence[torch.Tensor]) -> Optional[tuple[torch.Tensor, torch.Tensor]]:
+    """The fused ``(q [sum N, K], scale [sum N])`` view over the valid copies of weights that were quantised as one
+    group (their copies are row slices of one buffer, back to back); None otherwise."""
+    cs = [w8_of(w) for w in weights]  # (every member is checked, so every stale copy is dropped)
+    if any(c is None for c in cs):
+        return None
+    if len(cs) == 1:
+        return cs[0] if cs[0][0].is_contiguous() else None  # type: ignore[index]
+    q0, s0 = cs[0]  # type: ignore[misc]
+    K = q0.shape[1]
+    qn, sn, rows = q0.data_ptr(), s0.data_ptr(), 0
+    for q, s in cs:  # type: ignore[misc]
+        if not (q.is_contiguous() and s.is_contiguous() and q.shape[1] == K and q.dtype == q0.dtype
+                and q.data_ptr() == qn and s.data_ptr() == sn
+                and q.untyped_storage().data_ptr() == q0.untyped_storage().data_ptr()
+                and s.untyped_storage().data_ptr() == s0.untyped_storage().data_ptr()):
+            return None
+        qn += q.numel() * q.element_size()
+        sn += s.numel() * s.element_size()
+        rows += q.shape[0]
+    return torch.as_strided(q0, (rows, K), (K, 1)), torch.as_strided(s0, (rows,), (1,))
+
+
+@torch.no_grad()
+def quantize_parameters(weights: Sequence[torch.Tensor]) -> tuple[int, int]:
+    """Quantises a group of 2-D bf16 weights that share their input (one ``[sum N, K]`` buffer of codes and one
+    ``[sum N]`` buffer of scales; each member's copy is a row slice), overwrites each weight with its dequantised
+    values and attaches the copies.  Returns ``(bf16 bytes, fp8 bytes incl. scales)``."""
+    for w in weights:
+        if w.dim() != 2 or w.dtype != torch.bfloat16:
+            raise ValueError("quantize_parameters: 2-D bfloat16 weights only")
+    q, s = quantize_rows_fp8(torch.cat([w.detach() for w in weights], dim=0) if len(weights) > 1 else weights[0].detach())
+    q, s = q.contiguous(), s.contiguous()
+    deq = dequantize_rows_fp8(q, s, torch.bfloat16)
+    off = 0
+    for w in weights:
+        n = w.shape[0]
+        w.copy_(deq[off : off + n])
+        attach_w8(w, q[off : off + n], s[off : off + n])
+        off += n
+    return deq.numel() * 2, q.numel() + s.numel() * 4

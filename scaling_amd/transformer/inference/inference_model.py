@@ -10,6 +10,7 @@ import torch
 import yaml
 
 from ...core import BaseLayerIO, LayerSpec, PipePartitionMethod
+from ...core.nn.linear.main_grad import invalidate_transposed_weights
 from ...core.nn.parallel_module.inference_module import InferenceModule, RecorderSetting
 from ..context.config import TransformerArchitectureConfig
 from ..data import TextDatasetBatch
@@ -45,8 +46,10 @@ class TransformerInferenceModule(InferenceModule):
     def from_checkpoint(cls, checkpoint_dir: Path, devices: Sequence[Any] = (0,),
                         pipe_partition_method: PipePartitionMethod = PipePartitionMethod.UNIFORM,
                         pipe_partition_overwrite: Optional[list[int]] = None, config_file: Optional[Path] = None,
-                        vocab_file: Optional[Path] = None) -> "TransformerInferenceModule":
-        """Weights, ``config.yml`` and ``vocab.json`` are expected in the checkpoint directory by default."""
+                        vocab_file: Optional[Path] = None,
+                        weight_quantization: Optional[str] = None) -> "TransformerInferenceModule":
+        """Weights, ``config.yml`` and ``vocab.json`` are expected in the checkpoint directory by default.
+        ``weight_quantization`` (``"fp8_e4m3"``): ``quantize_weights`` is called after loading."""
         checkpoint_dir = Path(checkpoint_dir)
         config_file = config_file or checkpoint_dir / "config.yml"
         vocab_file = vocab_file or checkpoint_dir / "vocab.json"
@@ -57,7 +60,91 @@ class TransformerInferenceModule(InferenceModule):
                     pipe_partition_method=pipe_partition_method, pipe_partition_overwrite=pipe_partition_overwrite,
                     tokenizer=Tokenizer.from_file(str(vocab_file)))
         model.load_checkpoint(checkpoint_dir)
+        if weight_quantization is not None:
+            model.quantize_weights(weight_quantization)
         return model
+
+    def _quantization_groups(self, include_lm_head: bool) -> tuple[list[tuple[list[str], list[torch.Tensor]]], dict[str, str]]:
+        """``([(names, weights sharing one input), ...], {name: reason it is never quantised})`` of this model."""
+        from ...core.nn.mlp import ParallelSwiGLUMLP
+        from ..model.layers import TransformerLayer, TransformerLMHead, TransformerLMHeadTied
+
+        groups: list[tuple[list[str], list[torch.Tensor]]] = []
+        skipped: dict[str, str] = {}
+
+        def add(li: int, prefix: str, mods: list[tuple[str, torch.nn.Module]]) -> None:
+            groups.append(([f"{li}.{prefix}{n}.weight" for n, _ in mods], [m.weight for _, m in mods]))
+
+        for li, layer in enumerate(self._layers):
+            topo = getattr(layer, "topology", None)
+            if topo is not None and topo.config.model_parallel_size > 1:
+                raise RuntimeError("quantize_weights: tensor parallelism (model_parallel_size > 1) is not supported")
+            if isinstance(layer, TransformerLayer):
+                att, mlp = layer.self_attention, layer.mlp
+                if att.lora_config is not None and not att.lora_merged_state:
+                    raise RuntimeError("quantize_weights: merge the LoRA adapters first (unmerged adapters read the "
+                                       "bf16 weights they would be merged into)")
+                if att.qkv_in_one:
+                    add(li, "self_attention.", [("query_key_value", att.query_key_value)])
+                else:
+                    add(li, "self_attention.", [("query", att.query), ("key", att.key), ("value", att.value)])
+                add(li, "self_attention.", [("dense", att.dense)])
+                if isinstance(mlp, ParallelSwiGLUMLP):
+                    add(li, "mlp.", [("dense_in", mlp.dense_in), ("siglu_weight", mlp.siglu_weight)])
+                else:
+                    add(li, "mlp.", [("dense_in", mlp.dense_in)])
+                add(li, "mlp.", [("dense_out", mlp.dense_out)])
+            elif isinstance(layer, TransformerLMHeadTied):
+                if include_lm_head:
+                    skipped[f"{li}.lm_head"] = "tied to the embedding"
+            elif isinstance(layer, TransformerLMHead):
+                if include_lm_head:
+                    add(li, "", [("linear", layer.linear)])
+        return groups, skipped
+
+    def quantize_weights(self, scheme: str = "fp8_e4m3", include_lm_head: bool = False) -> dict:
+        """Opt-in FP8 weight-only decoding (``ops/quant.py``, ``csrc/kernels/gemv_fp8.hip``).
+
+        Every transformer layer's linear weights (q/k/v or fused qkv, attention dense, the MLP projections), and the
+        LM head when asked (never a tied head, embeddings, norms or biases), get an OCP e4m3 copy with one
+        power-of-two fp32 scale per output row, and the bf16 parameter is overwritten with the dequantised values:
+        the copy is an exact encoding of the parameter.  Decode-sized linear layers (<= 4 rows) then stream the
+        copy; the prefill GEMMs and every other path compute the same function from the bf16 parameters, which are
+        kept (weights take 1.5x their bf16 memory: the mode trades memory for bytes per token).  Modifying a
+        quantised parameter afterwards drops its copy (with a warning) and that layer decodes from bf16 again.
+
+        On a CPU module the parameters are replaced by the dequantised values and the copies are kept but unused
+        (the CPU path computes from the parameters).  Returns a summary: ``tensors``, ``bf16_bytes``, ``fp8_bytes``,
+        ``skipped`` (``{name: reason}``; a weight whose K is not a multiple of 16 is skipped)."""
+        from ...core.nn.linear.main_grad import adjacent_weights
+        from ...ops import quant
+
+        if scheme != quant.SCHEME:
+            raise ValueError(f"quantize_weights: unknown scheme {scheme!r} (supported: {quant.SCHEME!r})")
+        if self.devices is None or len(self.devices) != 1:
+            raise RuntimeError("quantize_weights: the model must sit on one device")
+        groups, skipped = self._quantization_groups(include_lm_head)
+        for names, weights in groups:
+            for n, w in zip(names, weights):
+                if w.dtype != torch.bfloat16:
+                    raise RuntimeError(f"quantize_weights: bfloat16 models only ({n} is {w.dtype}); in fp16 the "
+                                       "dequantised values would not be exact")
+                if w.device != self.devices[0]:
+                    raise RuntimeError(f"quantize_weights: {n} is on {w.device}, the model on {self.devices[0]}")
+        summary = {"scheme": scheme, "tensors": 0, "bf16_bytes": 0, "fp8_bytes": 0, "skipped": skipped}
+        for names, weights in groups:
+            if any(w.dim() != 2 or w.shape[1] % quant.PIECE for w in weights):
+                for n in names:
+                    skipped[n] = f"K is not a multiple of {quant.PIECE}"
+                continue
+            if len(weights) > 1:
+                adjacent_weights(weights)  # the fused bf16 view's re-homing must precede the copies' version stamps
+            b16, b8 = quant.quantize_parameters(weights)
+            summary["tensors"] += len(weights)
+            summary["bf16_bytes"] += b16
+            summary["fp8_bytes"] += b8
+        invalidate_transposed_weights()
+        return summary
 
     def forward(self, x: BaseLayerIO) -> TransformerLayerIO:
         out = super().forward(x)

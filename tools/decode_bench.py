@@ -1,6 +1,11 @@
 """Batch-1 decode latency on one GPU: eager cached generation vs HIP-graph-captured decoding, greedy or sampled.
 
     python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64] [--sampler T,K,P | torch:T,K,P]
+                                 [--weights fp8_e4m3 [--lm-head]]
+
+``--weights fp8_e4m3`` decodes the model after ``quantize_weights()`` (FP8 weight-only decoding; ``--lm-head`` includes
+the LM head); ``weights_gib`` and ``graph_gb_per_s`` then count what one decode step streams (the FP8 copies in place of
+their bf16 parameters).
 
 ``--sampler 0.8,40,0.95`` decodes with the fused ``Sampler`` (temperature, top-k, top-p) in both loops;
 ``--sampler torch:0.8,40,0.95`` times the eager loop with the torch composition
@@ -30,6 +35,8 @@ def main() -> None:
     p.add_argument("--tokens", type=int, default=64)
     p.add_argument("--num-layers", type=int, default=None)
     p.add_argument("--sampler", default=None, help="T,K,P: fused Sampler; torch:T,K,P: torch composition (eager only)")
+    p.add_argument("--weights", default="bf16", choices=["bf16", "fp8_e4m3"], help="fp8_e4m3: quantize_weights() first")
+    p.add_argument("--lm-head", action="store_true", help="with --weights fp8_e4m3: quantise the LM head too")
     a = p.parse_args()
     from scaling_amd.models import llama_architecture
     from scaling_amd.transformer.context.config import TransformerArchitectureConfig
@@ -47,6 +54,9 @@ def main() -> None:
     torch.manual_seed(0)
     m = TransformerInferenceModule(get_transformer_layer_specs(arch), devices=(0,))
     prompt = torch.randint(1, arch.vocab_size, (a.prompt,)).tolist()
+    quantised = None
+    if a.weights != "bf16":
+        quantised = m.quantize_weights(a.weights, include_lm_head=a.lm_head)
 
     sample_fn, graph_ok, mode = sample_argmax, True, "greedy"
     if a.sampler:
@@ -73,11 +83,16 @@ def main() -> None:
     tn, eager = timed(lambda: m.generate(a.tokens + 1, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn))
     eager_ms = 1000.0 * (tn - t1) / a.tokens
     weights = sum(p.numel() * p.element_size() for p in m.parameters())
+    extra = {"weights": a.weights}
+    if quantised is not None:  # a decode step streams the FP8 copies in place of their bf16 parameters
+        weights = weights - quantised["bf16_bytes"] + quantised["fp8_bytes"]
+        extra.update(lm_head=a.lm_head, quantised_tensors=quantised["tensors"], skipped=len(quantised["skipped"]),
+                     bf16_gib_replaced=round(quantised["bf16_bytes"] / 2**30, 2))
     if not graph_ok:
         print(json.dumps({
             "metric": metric, "sampler": mode, "model": a.model, "layers": arch.num_layers,
             "prompt": a.prompt, "tokens": a.tokens, "eager_ms_per_token": round(eager_ms, 3),
-            "weights_gib": round(weights / 2**30, 2),
+            "weights_gib": round(weights / 2**30, 2), **extra,
         }), flush=True)
         return
 
@@ -96,7 +111,7 @@ def main() -> None:
         "tokens": a.tokens, "eager_ms_per_token": round(eager_ms, 3), "graph_ms_per_token": round(graph_ms, 3),
         "speedup": round(eager_ms / graph_ms, 2), "graph_capture_ms": round(1000.0 * tc, 1),
         "graph_tokens_equal_eager": same, "weights_gib": round(weights / 2**30, 2),
-        "graph_gb_per_s": round(weights / (graph_ms * 1e-3) / 1e9, 1),
+        "graph_gb_per_s": round(weights / (graph_ms * 1e-3) / 1e9, 1), **extra,
     }), flush=True)
 
 

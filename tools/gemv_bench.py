@@ -1,5 +1,9 @@
-"""Decode GEMV micro-benchmark on one GPU: the 7B decode projections (q/k/v, o, gate/up, down) at batch 1 through
-the plain, epilogue-fused and norm-prologue GEMV kernels; prints us per call and the weight-stream rate."""
+"""Decode GEMV micro-benchmark on one GPU: the 7B decode projections (q/k/v, o, gate/up, down, head) at batch 1
+through the plain, epilogue-fused and norm-prologue GEMV kernels; prints us per call and the weight-stream rate.
+
+``FP8=1``: the FP8-weight kernels (``csrc/kernels/gemv_fp8.hip``) of the decode step, each right after its bf16
+counterpart, in the same process, on the same shapes and under the same cold-cache protocol (``PASSES`` alternating
+passes over the list, default 2 with FP8); the rate counts the bytes each kernel streams (codes + row scales)."""
 from __future__ import annotations
 
 import os
@@ -35,6 +39,14 @@ def copies(shape, dev, dt, cold: bool):
     return [torch.randn(*shape, device=dev, dtype=dt) / 64 for _ in range(n)]
 
 
+def copies8(shape, dev, cold: bool):
+    """FP8 copies ``(q, scale)`` under the same protocol: > 1 GiB of codes in total when cold."""
+    from scaling_amd.ops.quant import quantize_rows_fp8
+
+    n = max(2, -(-(1 << 30) // (shape[0] * shape[1]))) if cold else 1
+    return [quantize_rows_fp8(torch.randn(*shape, device=dev, dtype=torch.bfloat16) / 64) for _ in range(n)]
+
+
 def main() -> None:
     from scaling_amd.ops._ext import ext
     from scaling_amd.ops import norm as norm_ops
@@ -51,6 +63,8 @@ def main() -> None:
     wgu = copies((2 * F, H), dev, dt, cold)
     wd = copies((H, F), dev, dt, cold)
     a = torch.randn(M, F, device=dev, dtype=dt)
+    V = 32000
+    wh = copies((V, H), dev, dt, cold)
     W = lambda ws, i: ws[i % len(ws)]  # noqa: E731
     cases = [
         ("norm_row (rmsnorm, 1 launch)", lambda i: norm_ops.add_rms_norm(x, add, g, 1e-5), None),
@@ -61,12 +75,30 @@ def main() -> None:
         ("gate/up gemv_swiglu", lambda i: ext().gemv_swiglu(x, W(wgu, i)), wgu),
         ("gate/up gemv_norm swiglu", lambda i: ext().gemv_norm(x, add, g, 1e-5, W(wgu, i), 2), wgu),
         ("down gemv_residual", lambda i: ext().gemv_residual(a, W(wd, i), add), wd),
+        ("head gemv", lambda i: ext().gemv(x, W(wh, i), None), wh),
     ]
+    fp8 = os.environ.get("FP8", "0") != "0"
+    if fp8:
+        q_qkv, q_o, q_gu = copies8((3 * H, H), dev, cold), copies8((H, H), dev, cold), copies8((2 * F, H), dev, cold)
+        q_d, q_h = copies8((H, F), dev, cold), copies8((V, H), dev, cold)
+        after = {
+            "qkv gemv_norm": ("qkv gemv_w8_norm", lambda i: ext().gemv_w8_norm(x, None, g, 1e-5, *W(q_qkv, i), 0), q_qkv),
+            "o gemv_residual": ("o gemv_w8_residual", lambda i: ext().gemv_w8_residual(x, *W(q_o, i), add), q_o),
+            "gate/up gemv_norm swiglu": ("gate/up gemv_w8_norm swiglu",
+                                         lambda i: ext().gemv_w8_norm(x, add, g, 1e-5, *W(q_gu, i), 2), q_gu),
+            "down gemv_residual": ("down gemv_w8_residual", lambda i: ext().gemv_w8_residual(a, *W(q_d, i), add), q_d),
+            "head gemv": ("head gemv_w8", lambda i: ext().gemv_w8(x, *W(q_h, i), None), q_h),
+        }
+        cases = [c for case in cases for c in ([case, after[case[0]]] if case[0] in after else [case])]
     print(f"rows {M}, {'cold (weights cycled through > 1 GiB)' if cold else 'warm (one weight copy)'}", flush=True)
-    for name, fn, w in cases:
-        us = timeit(fn)
-        nb = w[0].numel() * w[0].element_size() if w is not None else 0
-        print(f"{name:34s} {us:8.2f} us  {nb / us / 1e6 if nb else 0:6.2f} TB/s", flush=True)
+    for p in range(int(os.environ.get("PASSES", "2" if fp8 else "1"))):
+        if fp8:
+            print(f"pass {p}", flush=True)
+        for name, fn, w in cases:
+            us = timeit(fn)
+            w0 = w[0] if w is not None else None
+            nb = sum(t.numel() * t.element_size() for t in (w0 if isinstance(w0, tuple) else (w0,))) if w0 is not None else 0
+            print(f"{name:34s} {us:8.2f} us  {nb / us / 1e6 if nb else 0:6.2f} TB/s", flush=True)
 
 
 if __name__ == "__main__":
