@@ -337,88 +337,146 @@ at::Tensor transpose2d(const at::Tensor& x) {
     return out;
 }
 
-// ------------------------------------------------------------------ GEMV (decode-time linear layers)
-// y[M, N] = x[M, K] W[N, K]^T (+ b), M <= 4, bf16 / fp16, unit inner strides, 16-B aligned rows
-bool gemv_ok(const at::Tensor& x, const at::Tensor& W) {
+// ------------------------------------------------------------------ GEMV (decode-time linear layers, gemv.hip)
+// y[M, N] = x[M, K] W[N, K]^T (+ b), M <= 4, unit inner strides, 16-B aligned rows.  Two weight formats:
+//  * dense (scale == nullptr): W of x's type, bf16 / fp16; 16-byte pieces of 8 weights: K % 8 == 0;
+//  * FP8 (the gemv_w8* names): W = scale[n] * Q[n, :], Q [N, K] OCP e4m3fn codes (float8_e4m3fn, or the same bytes
+//    as uint8), scale [N] fp32 powers of two (ops/quant.py); x bf16.  16-byte pieces of 16 codes: K % 16 == 0, Q rows
+//    a multiple of 16 bytes apart, 16-byte aligned bases.
+// Each pair of bound functions is one worker; name is the bound function's, for the error messages.
+bool gemv_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale) {
+    const int64_t P = scale ? 16 : 8;  // weights per 16-byte piece
     if (!(x.is_cuda() && W.is_cuda() && x.dim() == 2 && W.dim() == 2)) return false;
-    if (x.scalar_type() != W.scalar_type() || (x.scalar_type() != at::kBFloat16 && x.scalar_type() != at::kHalf))
+    if (scale) {
+        if (!(scale->is_cuda() && scale->dim() == 1) || W.device() != x.device() || scale->device() != x.device())
+            return false;
+        if (x.scalar_type() != at::kBFloat16 || (W.scalar_type() != at::kFloat8_e4m3fn && W.scalar_type() != at::kByte))
+            return false;
+        if (scale->scalar_type() != at::kFloat || scale->numel() != W.size(0) || !scale->is_contiguous() ||
+            (uintptr_t)scale->data_ptr() % 4 != 0)
+            return false;
+        if (x.size(1) < 16 || W.stride(0) < W.size(1)) return false;
+    } else if (x.scalar_type() != W.scalar_type() || (x.scalar_type() != at::kBFloat16 && x.scalar_type() != at::kHalf)) {
         return false;
-    if (x.size(0) < 1 || x.size(0) > 4 || x.size(1) != W.size(1) || x.size(1) % 8 != 0 || W.size(0) < 1) return false;
-    if (x.stride(1) != 1 || W.stride(1) != 1 || (x.size(0) > 1 && x.stride(0) % 8 != 0) || W.stride(0) % 8 != 0)
+    }
+    if (x.size(0) < 1 || x.size(0) > 4 || x.size(1) != W.size(1) || x.size(1) % P != 0 || W.size(0) < 1) return false;
+    if (x.stride(1) != 1 || W.stride(1) != 1 || (x.size(0) > 1 && x.stride(0) % 8 != 0) || W.stride(0) % P != 0)
         return false;
     return (uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)W.data_ptr() % 16 == 0;
 }
-at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, c10::optional<at::Tensor> bias) {
-    TORCH_CHECK(gemv_ok(x, W), "gemv: unsupported operands (x [M<=4, K], W [N, K], bf16/fp16, K % 8 == 0, aligned)");
+bool gemv_norm_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale, const at::Tensor& gamma) {
+    if (!gemv_operands_ok(x, W, scale) || !x.is_contiguous()) return false;
+    return gamma.is_cuda() && gamma.dim() == 1 && gamma.numel() == x.size(1) && gamma.is_contiguous() &&
+           gamma.scalar_type() == x.scalar_type() && (uintptr_t)gamma.data_ptr() % 16 == 0;
+}
+const float* scale_ptr(const at::Tensor* scale) { return scale ? scale->data_ptr<float>() : nullptr; }
+
+at::Tensor gemv_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
+                     const c10::optional<at::Tensor>& bias) {
+    TORCH_CHECK(gemv_operands_ok(x, W, scale), name, ": unsupported operands ",
+                scale ? "(x bf16 [M<=4, K], Q e4m3fn [N, K], scale fp32 [N], K % 16 == 0, 16-byte aligned rows)"
+                      : "(x [M<=4, K], W [N, K], bf16/fp16, K % 8 == 0, aligned)");
     const at::DeviceGuard g(x.device());
     const int64_t M = x.size(0), N = W.size(0), K = W.size(1);
     const void* bp = nullptr;
     at::Tensor bc;
     if (bias.has_value() && bias->defined()) {
-        TORCH_CHECK(bias->numel() == N && bias->scalar_type() == W.scalar_type(), "gemv: bias");
+        TORCH_CHECK(bias->is_cuda() && bias->numel() == N && bias->scalar_type() == x.scalar_type(), name, ": bias");
         bc = bias->contiguous();
         bp = bc.data_ptr();
     }
     auto y = at::empty({M, N}, x.options());
-    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), bp, y.data_ptr(), N, (int)N,
-                    (int)K, cur_stream());
+    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), bp, y.data_ptr(), N,
+                    (int)N, (int)K, cur_stream());
     return y;
 }
 // decode epilogues: y = rnd(x W^T) + res  (res [M, N]) ...
-at::Tensor gemv_residual(const at::Tensor& x, const at::Tensor& W, const at::Tensor& res) {
-    TORCH_CHECK(gemv_ok(x, W), "gemv_residual: unsupported operands");
+at::Tensor gemv_residual_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
+                              const at::Tensor& res) {
+    TORCH_CHECK(gemv_operands_ok(x, W, scale), name, ": unsupported operands");
     const int64_t M = x.size(0), N = W.size(0), K = W.size(1);
     TORCH_CHECK(res.is_cuda() && res.dim() == 2 && res.size(0) == M && res.size(1) == N && res.stride(1) == 1 &&
-                    res.scalar_type() == x.scalar_type(), "gemv_residual: res must be [M, N] of the input dtype");
+                    res.scalar_type() == x.scalar_type(), name, ": res must be [M, N] of the input dtype");
     const at::DeviceGuard g(x.device());
     auto y = at::empty({M, N}, x.options());
-    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), nullptr, y.data_ptr(), N, (int)N,
-                    (int)K, cur_stream(), 1, res.data_ptr(), res.stride(0));
+    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
+                    y.data_ptr(), N, (int)N, (int)K, cur_stream(), 1, res.data_ptr(), res.stride(0));
     return y;
 }
 // ... and SwiGLU over W = [gate; up] ([2F, K]): y[:, n] = silu(x W_gate^T)[n] * (x W_up^T)[n], rounded as gemv + swiglu
-at::Tensor gemv_swiglu(const at::Tensor& x, const at::Tensor& W) {
-    TORCH_CHECK(gemv_ok(x, W) && W.size(0) % 2 == 0, "gemv_swiglu: unsupported operands");
+// (FP8: scale [2F], the halves keep their own row scales)
+at::Tensor gemv_swiglu_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale) {
+    TORCH_CHECK(gemv_operands_ok(x, W, scale) && W.size(0) % 2 == 0, name, ": unsupported operands");
     const int64_t M = x.size(0), F = W.size(0) / 2, K = W.size(1);
     const at::DeviceGuard g(x.device());
     auto y = at::empty({M, F}, x.options());
-    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), nullptr, y.data_ptr(), F, (int)F,
-                    (int)K, cur_stream(), 2, nullptr, 0);
+    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
+                    y.data_ptr(), F, (int)F, (int)K, cur_stream(), 2, nullptr, 0);
     return y;
 }
 // ... with the RMSNorm in front fused into the same pass: s = x (+ add); y = gemv(rms_norm(s, gamma, eps), W) with
 // epi 0 (plain) or 2 (SwiGLU over [gate; up]), the normalised row kept in fp32; returns (s, y), s written by the
 // kernel when add is given
-bool gemv_norm_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor& gamma) {
-    if (!gemv_ok(x, W) || !x.is_contiguous()) return false;
-    if (!(gamma.is_cuda() && gamma.dim() == 1 && gamma.numel() == x.size(1) && gamma.is_contiguous() &&
-          gamma.scalar_type() == x.scalar_type() && (uintptr_t)gamma.data_ptr() % 16 == 0))
-        return false;
-    return true;
-}
-std::vector<at::Tensor> gemv_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
-                                  double eps, const at::Tensor& W, int64_t epi) {
-    TORCH_CHECK(gemv_norm_ok(x, W, gamma) && (epi == 0 || (epi == 2 && W.size(0) % 2 == 0)),
-                "gemv_norm: unsupported operands");
+std::vector<at::Tensor> gemv_norm_impl(const char* name, const at::Tensor& x, const c10::optional<at::Tensor>& add,
+                                       const at::Tensor& gamma, double eps, const at::Tensor& W, const at::Tensor* scale,
+                                       int64_t epi) {
+    TORCH_CHECK(gemv_norm_operands_ok(x, W, scale, gamma) && (epi == 0 || (epi == 2 && W.size(0) % 2 == 0)), name,
+                ": unsupported operands");
     const int64_t M = x.size(0), K = W.size(1), N = epi == 2 ? W.size(0) / 2 : W.size(0);
     const at::DeviceGuard g(x.device());
     at::Tensor s = x;
     const void* ap = nullptr;
     if (add.has_value() && add->defined()) {
-        TORCH_CHECK(add->sizes() == x.sizes() && add->is_contiguous() && add->scalar_type() == x.scalar_type() &&
-                        (uintptr_t)add->data_ptr() % 16 == 0, "gemv_norm: add must be a contiguous, aligned [M, K]");
+        TORCH_CHECK(add->is_cuda() && add->sizes() == x.sizes() && add->is_contiguous() &&
+                        add->scalar_type() == x.scalar_type() && (uintptr_t)add->data_ptr() % 16 == 0,
+                    name, ": add must be a contiguous, aligned [M, K]");
         s = at::empty_like(x);
         ap = add->data_ptr();
     }
     auto y = at::empty({M, N}, x.options());
-    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), nullptr, y.data_ptr(), N, (int)N,
-                    (int)K, cur_stream(), (int)epi, nullptr, 0, gamma.data_ptr(), ap, ap ? s.data_ptr() : nullptr,
-                    (float)eps);
+    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
+                    y.data_ptr(), N, (int)N, (int)K, cur_stream(), (int)epi, nullptr, 0, gamma.data_ptr(), ap,
+                    ap ? s.data_ptr() : nullptr, (float)eps);
     return {s, y};
 }
+
+bool gemv_ok(const at::Tensor& x, const at::Tensor& W) { return gemv_operands_ok(x, W, nullptr); }
+at::Tensor gemv(const at::Tensor& x, const at::Tensor& W, c10::optional<at::Tensor> bias) {
+    return gemv_impl("gemv", x, W, nullptr, bias);
+}
+at::Tensor gemv_residual(const at::Tensor& x, const at::Tensor& W, const at::Tensor& res) {
+    return gemv_residual_impl("gemv_residual", x, W, nullptr, res);
+}
+at::Tensor gemv_swiglu(const at::Tensor& x, const at::Tensor& W) { return gemv_swiglu_impl("gemv_swiglu", x, W, nullptr); }
+bool gemv_norm_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor& gamma) {
+    return gemv_norm_operands_ok(x, W, nullptr, gamma);
+}
+std::vector<at::Tensor> gemv_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
+                                  double eps, const at::Tensor& W, int64_t epi) {
+    return gemv_norm_impl("gemv_norm", x, add, gamma, eps, W, nullptr, epi);
+}
+bool gemv_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) { return gemv_operands_ok(x, Q, &scale); }
+at::Tensor gemv_w8(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, c10::optional<at::Tensor> bias) {
+    return gemv_impl("gemv_w8", x, Q, &scale, bias);
+}
+at::Tensor gemv_w8_residual(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& res) {
+    return gemv_residual_impl("gemv_w8_residual", x, Q, &scale, res);
+}
+at::Tensor gemv_w8_swiglu(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    return gemv_swiglu_impl("gemv_w8_swiglu", x, Q, &scale);
+}
+bool gemv_w8_norm_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& gamma) {
+    return gemv_norm_operands_ok(x, Q, &scale, gamma);
+}
+std::vector<at::Tensor> gemv_w8_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
+                                     double eps, const at::Tensor& Q, const at::Tensor& scale, int64_t epi) {
+    return gemv_norm_impl("gemv_w8_norm", x, add, gamma, eps, Q, &scale, epi);
+}
+
 // graph-decode q/k/v step in ONE launch: q = RoPE(rms_norm(x) Wq^T) is returned, RoPE(rms_norm(x) Wk^T) and
 // rms_norm(x) Wv^T are written into the K / V cache rows at the device-side position pos (interleaved rotary pairs,
 // rotary dims rd of hd; x one token).  None when the operands do not fit (the caller runs gemv_norm + rope_kv_append).
+// Dense weights only.
 c10::optional<at::Tensor> gemv_norm_rope(const at::Tensor& x, const at::Tensor& gamma, double eps, const at::Tensor& W,
                                          const at::Tensor& cosb, const at::Tensor& sinb, const at::Tensor& pos,
                                          int64_t nq, int64_t nkv, int64_t rd, at::Tensor kc, at::Tensor vc,
@@ -439,93 +497,10 @@ c10::optional<at::Tensor> gemv_norm_rope(const at::Tensor& x, const at::Tensor& 
     GemvRope r{cosb.data_ptr<float>(), sinb.data_ptr<float>(), pos.data_ptr<int64_t>(), q.data_ptr(), kc.data_ptr(),
                vc.data_ptr(), (int)nq, (int)nkv, (int)hd, (int)rd, std::min<int64_t>(kc.size(0), cosb.size(0)),
                err.data_ptr<int>()};
-    sa_launch::gemv(dt(x), 1, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), nullptr, nullptr, 0,
+    sa_launch::gemv(dt(x), 1, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), nullptr, nullptr, nullptr, 0,
                     (int)W.size(0), (int)W.size(1), cur_stream(), 3, nullptr, 0, gamma.data_ptr(), nullptr, nullptr,
                     (float)eps, &r);
     return q;
-}
-
-// ------------------------------------------------------------------ GEMV over FP8 weights (gemv_fp8.hip)
-// W = scale[n] * Q[n, :]: Q [N, K] OCP e4m3fn codes (float8_e4m3fn, or the same bytes as uint8), scale [N] fp32
-// powers of two (ops/quant.py); x bf16 [M <= 4, K].  16-byte pieces of 16 codes: K % 16 == 0, Q rows a multiple of
-// 16 bytes apart, 16-byte aligned bases.
-bool gemv_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
-    if (!(x.is_cuda() && Q.is_cuda() && scale.is_cuda() && x.dim() == 2 && Q.dim() == 2 && scale.dim() == 1)) return false;
-    if (Q.device() != x.device() || scale.device() != x.device()) return false;
-    if (x.scalar_type() != at::kBFloat16 || (Q.scalar_type() != at::kFloat8_e4m3fn && Q.scalar_type() != at::kByte))
-        return false;
-    if (scale.scalar_type() != at::kFloat || scale.numel() != Q.size(0) || !scale.is_contiguous()) return false;
-    if (x.size(0) < 1 || x.size(0) > 4 || x.size(1) != Q.size(1) || x.size(1) % 16 != 0 || x.size(1) < 16 || Q.size(0) < 1)
-        return false;
-    if (x.stride(1) != 1 || Q.stride(1) != 1 || (x.size(0) > 1 && x.stride(0) % 8 != 0) || Q.stride(0) % 16 != 0 ||
-        Q.stride(0) < Q.size(1))
-        return false;
-    return (uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)Q.data_ptr() % 16 == 0 && (uintptr_t)scale.data_ptr() % 4 == 0;
-}
-at::Tensor gemv_w8(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, c10::optional<at::Tensor> bias) {
-    TORCH_CHECK(gemv_w8_ok(x, Q, scale), "gemv_w8: unsupported operands (x bf16 [M<=4, K], Q e4m3fn [N, K], scale fp32 "
-                                         "[N], K % 16 == 0, 16-byte aligned rows)");
-    const at::DeviceGuard g(x.device());
-    const int64_t M = x.size(0), N = Q.size(0), K = Q.size(1);
-    const void* bp = nullptr;
-    at::Tensor bc;
-    if (bias.has_value() && bias->defined()) {
-        TORCH_CHECK(bias->is_cuda() && bias->numel() == N && bias->scalar_type() == x.scalar_type(), "gemv_w8: bias");
-        bc = bias->contiguous();
-        bp = bc.data_ptr();
-    }
-    auto y = at::empty({M, N}, x.options());
-    sa_launch::gemv_w8((int)M, x.data_ptr(), x.stride(0), Q.data_ptr(), Q.stride(0), scale.data_ptr<float>(), bp,
-                       y.data_ptr(), N, (int)N, (int)K, cur_stream());
-    return y;
-}
-at::Tensor gemv_w8_residual(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& res) {
-    TORCH_CHECK(gemv_w8_ok(x, Q, scale), "gemv_w8_residual: unsupported operands");
-    const int64_t M = x.size(0), N = Q.size(0), K = Q.size(1);
-    TORCH_CHECK(res.is_cuda() && res.dim() == 2 && res.size(0) == M && res.size(1) == N && res.stride(1) == 1 &&
-                    res.scalar_type() == x.scalar_type(), "gemv_w8_residual: res must be [M, N] of the input dtype");
-    const at::DeviceGuard g(x.device());
-    auto y = at::empty({M, N}, x.options());
-    sa_launch::gemv_w8((int)M, x.data_ptr(), x.stride(0), Q.data_ptr(), Q.stride(0), scale.data_ptr<float>(), nullptr,
-                       y.data_ptr(), N, (int)N, (int)K, cur_stream(), 1, res.data_ptr(), res.stride(0));
-    return y;
-}
-// SwiGLU over Q = [gate; up] ([2F, K], scale [2F]: the halves keep their own row scales)
-at::Tensor gemv_w8_swiglu(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
-    TORCH_CHECK(gemv_w8_ok(x, Q, scale) && Q.size(0) % 2 == 0, "gemv_w8_swiglu: unsupported operands");
-    const int64_t M = x.size(0), F = Q.size(0) / 2, K = Q.size(1);
-    const at::DeviceGuard g(x.device());
-    auto y = at::empty({M, F}, x.options());
-    sa_launch::gemv_w8((int)M, x.data_ptr(), x.stride(0), Q.data_ptr(), Q.stride(0), scale.data_ptr<float>(), nullptr,
-                       y.data_ptr(), F, (int)F, (int)K, cur_stream(), 2, nullptr, 0);
-    return y;
-}
-bool gemv_w8_norm_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& gamma) {
-    if (!gemv_w8_ok(x, Q, scale) || !x.is_contiguous()) return false;
-    return gamma.is_cuda() && gamma.dim() == 1 && gamma.numel() == x.size(1) && gamma.is_contiguous() &&
-           gamma.scalar_type() == x.scalar_type() && (uintptr_t)gamma.data_ptr() % 16 == 0;
-}
-// (s, y) as gemv_norm: s = x (+ add); y = gemv_w8(rms_norm(s, gamma, eps), Q, scale), epi 0 plain or 2 SwiGLU
-std::vector<at::Tensor> gemv_w8_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
-                                     double eps, const at::Tensor& Q, const at::Tensor& scale, int64_t epi) {
-    TORCH_CHECK(gemv_w8_norm_ok(x, Q, scale, gamma) && (epi == 0 || (epi == 2 && Q.size(0) % 2 == 0)),
-                "gemv_w8_norm: unsupported operands");
-    const int64_t M = x.size(0), K = Q.size(1), N = epi == 2 ? Q.size(0) / 2 : Q.size(0);
-    const at::DeviceGuard g(x.device());
-    at::Tensor s = x;
-    const void* ap = nullptr;
-    if (add.has_value() && add->defined()) {
-        TORCH_CHECK(add->is_cuda() && add->sizes() == x.sizes() && add->is_contiguous() &&
-                        add->scalar_type() == x.scalar_type() && (uintptr_t)add->data_ptr() % 16 == 0,
-                    "gemv_w8_norm: add must be a contiguous, aligned [M, K]");
-        s = at::empty_like(x);
-        ap = add->data_ptr();
-    }
-    auto y = at::empty({M, N}, x.options());
-    sa_launch::gemv_w8((int)M, x.data_ptr(), x.stride(0), Q.data_ptr(), Q.stride(0), scale.data_ptr<float>(), nullptr,
-                       y.data_ptr(), N, (int)N, (int)K, cur_stream(), (int)epi, nullptr, 0, gamma.data_ptr(), ap,
-                       ap ? s.data_ptr() : nullptr, (float)eps);
-    return {s, y};
 }
 
 // ------------------------------------------------------------------ GEMM (weight gradient)

@@ -20,6 +20,19 @@
 // No prologue pass, no barrier, no extra launch: the two latency-bound norm launches per layer and token go away.
 // The wave that owns output row 0 also writes s (the new residual stream).  Eager and graph decoding both run this
 // kernel, so their tokens stay identical; against norm + GEMV it differs by the two skipped bf16 roundings.
+//
+// FP8 weights (E4M3W):  W = scale[n] * Q[n, :], Q OCP e4m3fn codes, one byte per weight, scale one fp32 power of two
+// per output row (scaling_amd/ops/quant.py), so the layer streams half the bytes of its bf16 form.  The same kernel
+// body, same launch rules, same rounding points; the weight format only changes
+//  * the piece: still 16 bytes per lane, which is now 16 weights: K % 16 == 0, two 16-byte loads of x (and of
+//    gamma / add for the NORM prologue) per piece and input row;
+//  * the decoding: the codes stay raw across the trip and are converted two at a time by the hardware
+//    (v_cvt_pk_f32_fp8, __builtin_amdgcn_cvt_pk_f32_fp8), once per piece and weight row, and reused by all M
+//    inputs; products and sums are fp32 as before;
+//  * the row scale, which multiplies the dot product ONCE per output row, after the wave / K-split reduction and
+//    before rstd, the bias and the epilogue: a power of two, so the result is the dot product with the dequantised
+//    bf16 weights up to the order of the fp32 sums.  SwiGLU: rows n and F + n each take their own scale.
+// FP8 weights take bf16 activations only, and the one-launch RoPE step (EPI_ROPE) has no FP8 form.
 #include "common.h"
 #include "launch.h"
 
@@ -30,6 +43,66 @@ using namespace sa;
 namespace {
 
 enum { EPI_NONE = 0, EPI_RES = 1, EPI_SWIGLU = 2, EPI_ROPE = 3 };
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+// Weight formats: T the element type of W's pointer arithmetic (ldw counts T's), P = 1 << kLog2P weights per 16-byte
+// piece, S one piece as it is held across a trip (ld) until piece() turns it into P floats (unpack).
+// Weights of the activation type E: converted to float at load time (staging them raw reschedules the whole kernel).
+template <typename E>
+struct DenseW {
+    typedef E T;
+    typedef float S[8];
+    static constexpr int kLog2P = 3, P = 8;
+    static constexpr bool kScaled = false;
+    __device__ static __forceinline__ void ld(const E* p, S& s) { V8<E>::ld(p, s); }
+    __device__ static __forceinline__ void unpack(const S& s, float (&v)[8]) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = s[i];
+    }
+};
+// e4m3fn codes with one fp32 scale per row (kScaled): 16 codes -> 16 floats, in memory order
+struct E4M3W {
+    typedef uint8_t T;
+    typedef u32x4 S;
+    static constexpr int kLog2P = 4, P = 16;
+    static constexpr bool kScaled = true;
+    __device__ static __forceinline__ void ld(const uint8_t* p, S& s) { s = *reinterpret_cast<const u32x4*>(p); }
+    __device__ static __forceinline__ void unpack(const S& r, float (&v)[16]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[i], false);
+            const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[i], true);
+            v[4 * i] = lo[0];
+            v[4 * i + 1] = lo[1];
+            v[4 * i + 2] = hi[0];
+            v[4 * i + 3] = hi[1];
+        }
+    }
+};
+
+// one P-element piece of x / gamma / add / sum: P / 8 16-byte loads or stores
+template <int P, typename E>
+__device__ __forceinline__ void ld_piece(const E* p, float (&v)[P]) {
+#pragma unroll
+    for (int h = 0; h < P / 8; ++h) {
+        float t[8];
+        V8<E>::ld(p + 8 * h, t);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[8 * h + i] = t[i];
+    }
+}
+template <int P, typename E>
+__device__ __forceinline__ void st_piece(E* p, const float (&v)[P]) {
+#pragma unroll
+    for (int h = 0; h < P / 8; ++h) {
+        float t[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t[i] = v[8 * h + i];
+        V8<E>::st(p + 8 * h, t);
+    }
+}
 
 template <typename E>
 struct NormArgs {
@@ -51,35 +124,39 @@ struct NormArgs {
 };
 
 // Streams this wave's share of K -- pieces g0, g0 + GS, ... (GS = 64 x waves per row) -- of NR weight rows against
-// all M inputs; returns the wave-reduced dot products acc and (NORM) sums of squares ss.
-template <int M, int NR, typename E, bool NORM>
-__device__ __forceinline__ void gemv_rows(const E* __restrict__ x, int64_t ldx, const E* const (&w)[NR], int K,
-                                          int g0, int GS, float (&acc)[NR][M], float (&ss)[M], const NormArgs<E>& na,
-                                          bool write_sum) {
+// all M inputs; returns the wave-reduced (unscaled) dot products acc and (NORM) sums of squares ss.
+template <int M, int NR, typename E, typename F, bool NORM>
+__device__ __forceinline__ void gemv_rows(const E* __restrict__ x, int64_t ldx, const typename F::T* const (&w)[NR],
+                                          int K, int g0, int GS, float (&acc)[NR][M], float (&ss)[M],
+                                          const NormArgs<E>& na, bool write_sum) {
+    constexpr int P = F::P;
 #pragma unroll
     for (int r = 0; r < NR; ++r)
 #pragma unroll
         for (int m = 0; m < M; ++m) acc[r][m] = 0.f;
 #pragma unroll
     for (int m = 0; m < M; ++m) ss[m] = 0.f;
-    // one 8-element piece p of every input row against the weight pieces wv (NR rows)
-    auto piece = [&](int p, const float (&wv)[NR][8]) {
-        float gv[8];
-        if constexpr (NORM) V8<E>::ld(na.g + 8 * p, gv);
+    // one P-element piece p of every input row against the staged weight pieces ws (NR rows)
+    auto piece = [&](int p, const typename F::S (&ws)[NR]) {
+        float wv[NR][P];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) F::unpack(ws[r], wv[r]);
+        float gv[P];
+        if constexpr (NORM) ld_piece<P>(na.g + P * p, gv);
 #pragma unroll
         for (int m = 0; m < M; ++m) {
-            float xv[8];
-            V8<E>::ld(x + m * ldx + 8 * p, xv);
+            float xv[P];
+            ld_piece<P>(x + m * ldx + P * p, xv);
             if constexpr (NORM) {
                 if (na.add != nullptr) {
-                    float av[8];
-                    V8<E>::ld(na.add + (int64_t)m * K + 8 * p, av);
+                    float av[P];
+                    ld_piece<P>(na.add + (int64_t)m * K + P * p, av);
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) xv[i] = rnd<E>(xv[i] + av[i]);
-                    if (write_sum) V8<E>::st(na.sum + (int64_t)m * K + 8 * p, xv);
+                    for (int i = 0; i < P; ++i) xv[i] = rnd<E>(xv[i] + av[i]);
+                    if (write_sum) st_piece<P>(na.sum + (int64_t)m * K + P * p, xv);
                 }
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
+                for (int i = 0; i < P; ++i) {
                     ss[m] = __builtin_fmaf(xv[i], xv[i], ss[m]);
                     xv[i] *= gv[i];
                 }
@@ -87,32 +164,32 @@ __device__ __forceinline__ void gemv_rows(const E* __restrict__ x, int64_t ldx, 
 #pragma unroll
             for (int r = 0; r < NR; ++r)
 #pragma unroll
-                for (int i = 0; i < 8; ++i) acc[r][m] = __builtin_fmaf(wv[r][i], xv[i], acc[r][m]);
+                for (int i = 0; i < P; ++i) acc[r][m] = __builtin_fmaf(wv[r][i], xv[i], acc[r][m]);
         }
     };
     constexpr int U = 4 / NR > 0 ? 4 / NR : 1;  // pieces per weight row per trip (4 KiB per wave)
-    const int G = K >> 3;                        // 8-element pieces per row
+    const int G = K >> F::kLog2P;                // P-element pieces per row
     int g = g0;
     for (; g + GS * (U - 1) < G; g += GS * U) {
-        float wv[U][NR][8];
+        typename F::S ws[U][NR];
 #pragma unroll
         for (int r = 0; r < NR; ++r)
 #pragma unroll
-            for (int u = 0; u < U; ++u) V8<E>::ld(w[r] + 8 * (g + GS * u), wv[u][r]);
+            for (int u = 0; u < U; ++u) F::ld(w[r] + P * (g + GS * u), ws[u][r]);
 #pragma unroll
-        for (int u = 0; u < U; ++u) piece(g + GS * u, wv[u]);
+        for (int u = 0; u < U; ++u) piece(g + GS * u, ws[u]);
     }
     if (g < G) {  // the ragged tail as ONE predicated trip
-        float wv[U][NR][8];
+        typename F::S ws[U][NR];
 #pragma unroll
         for (int u = 0; u < U; ++u)
             if (g + GS * u < G) {
 #pragma unroll
-                for (int r = 0; r < NR; ++r) V8<E>::ld(w[r] + 8 * (g + GS * u), wv[u][r]);
+                for (int r = 0; r < NR; ++r) F::ld(w[r] + P * (g + GS * u), ws[u][r]);
             }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (g + GS * u < G) piece(g + GS * u, wv[u]);
+            if (g + GS * u < G) piece(g + GS * u, ws[u]);
     }
 #pragma unroll
     for (int m = 0; m < M; ++m) {
@@ -137,25 +214,31 @@ __device__ __forceinline__ float pick(const float (&a)[M], int lane) {
 // KS waves per row (1 or 4): with few output rows (N = 4096: o / down projections) one wave per row leaves the CUs
 // a quarter occupied, so the workgroup's four waves split K (interleaved 1 KiB slices, the workgroup streams
 // contiguous 4 KiB) and reduce through LDS in a fixed order.
-template <int M, int EPI, typename E, bool NORM, int RPW, int KS>
-__global__ __launch_bounds__(256) void gemv_kernel(const E* __restrict__ x, int64_t ldx, const E* __restrict__ W,
-                                                   int64_t ldw, const E* __restrict__ bias, const E* __restrict__ res,
-                                                   int64_t ldr, E* __restrict__ y, int64_t ldy, int N, int K,
-                                                   NormArgs<E> na) {
+// F the weight format: W rows are ldw F::T's apart (elements, or bytes for FP8); scale is read when F::kScaled.
+template <int M, int EPI, typename E, typename F, bool NORM, int RPW, int KS>
+__global__ __launch_bounds__(256) void gemv_kernel(const E* __restrict__ x, int64_t ldx,
+                                                   const typename F::T* __restrict__ W, int64_t ldw,
+                                                   const float* __restrict__ scale, const E* __restrict__ bias,
+                                                   const E* __restrict__ res, int64_t ldr, E* __restrict__ y,
+                                                   int64_t ldy, int N, int K, NormArgs<E> na) {
+    static_assert(!F::kScaled || EPI != EPI_ROPE, "EPI_ROPE has no FP8 form");
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int row = (blockIdx.x * (4 / KS) + wv / KS) * RPW;
     const int kw = wv % KS;  // this wave's K slice
     if (row >= N) return;    // wave-uniform (N % RPW == 0); workgroup-uniform when KS == 4
     constexpr int NS = EPI == EPI_SWIGLU ? 2 : 1;  // weight rows per output row
     constexpr int NR = NS * RPW;
-    const E* w[NR];
+    const typename F::T* w[NR];
+    int wrow[NR];
 #pragma unroll
     for (int q = 0; q < RPW; ++q) {
-        w[q] = W + (int64_t)(row + q) * ldw;
-        if constexpr (NS == 2) w[RPW + q] = W + (int64_t)(row + q + N) * ldw;  // up row F + n
+        wrow[q] = row + q;
+        if constexpr (NS == 2) wrow[RPW + q] = row + q + N;  // up row F + n
     }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) w[r] = W + (int64_t)wrow[r] * ldw;
     float acc[NR][M], ss[M];
-    gemv_rows<M, NR, E, NORM>(x, ldx, w, K, lane + 64 * kw, 64 * KS, acc, ss, na, NORM && row == 0);  // row 0's waves write s
+    gemv_rows<M, NR, E, F, NORM>(x, ldx, w, K, lane + 64 * kw, 64 * KS, acc, ss, na, NORM && row == 0);  // row 0's waves write s
     if constexpr (KS > 1) {
         // partial sums of the K slices: waves 1..KS-1 -> LDS, wave 0 adds them in slice order
         __shared__ float red[KS][NR + 1][M];
@@ -177,6 +260,14 @@ __global__ __launch_bounds__(256) void gemv_kernel(const E* __restrict__ x, int6
                 for (int r = 0; r < NR; ++r) acc[r][m] += red[k][r][m];
                 ss[m] += red[k][NR][m];
             }
+    }
+    if constexpr (F::kScaled) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const float sc = scale[wrow[r]];  // the row's power of two: exact
+#pragma unroll
+            for (int m = 0; m < M; ++m) acc[r][m] *= sc;
+        }
     }
     if constexpr (NORM) {
 #pragma unroll
@@ -242,82 +333,103 @@ int rows_per_wave(bool norm, int N) {
 // (the 4096 x 11008 down projection), 1 for the plain projections
 int waves_per_row(bool split) { return split ? 4 : 1; }
 
-template <int EPI, typename E, bool NORM, int RPW, int KS>
-void launch_k(int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const void* b, const void* r, int64_t ldr,
-              void* y, int64_t ldy, int N, int K, hipStream_t st, NormArgs<E> na) {
+template <typename E, typename F>
+struct Args {
+    int M;
+    const E* x;
+    int64_t ldx;
+    const typename F::T* W;
+    int64_t ldw;
+    const float* scale;
+    const E* b;
+    const E* r;
+    int64_t ldr;
+    E* y;
+    int64_t ldy;
+    int N, K;
+    hipStream_t st;
+    NormArgs<E> na;
+};
+
+template <int M, int EPI, bool NORM, int RPW, int KS, typename E, typename F>
+void launch_m(const Args<E, F>& a) {
     constexpr int RB = 4 / KS * RPW;  // output rows per workgroup
-    const dim3 grid((unsigned)((N + RB - 1) / RB)), block(256);
-    const E *xp = (const E*)x, *wp = (const E*)W, *bp = (const E*)b, *rp = (const E*)r;
-    E* yp = (E*)y;
-    if constexpr (EPI == EPI_ROPE) {
-        hipLaunchKernelGGL((gemv_kernel<1, EPI, E, NORM, RPW, KS>), grid, block, 0, st, xp, ldx, wp, ldw, bp, rp, ldr, yp, ldy, N, K, na);
-        return;
-    }
-    switch (M) {
-        case 1: hipLaunchKernelGGL((gemv_kernel<1, EPI, E, NORM, RPW, KS>), grid, block, 0, st, xp, ldx, wp, ldw, bp, rp, ldr, yp, ldy, N, K, na); break;
-        case 2: hipLaunchKernelGGL((gemv_kernel<2, EPI, E, NORM, RPW, KS>), grid, block, 0, st, xp, ldx, wp, ldw, bp, rp, ldr, yp, ldy, N, K, na); break;
-        case 3: hipLaunchKernelGGL((gemv_kernel<3, EPI, E, NORM, RPW, KS>), grid, block, 0, st, xp, ldx, wp, ldw, bp, rp, ldr, yp, ldy, N, K, na); break;
-        default: hipLaunchKernelGGL((gemv_kernel<4, EPI, E, NORM, RPW, KS>), grid, block, 0, st, xp, ldx, wp, ldw, bp, rp, ldr, yp, ldy, N, K, na); break;
-    }
+    hipLaunchKernelGGL((gemv_kernel<M, EPI, E, F, NORM, RPW, KS>), dim3((unsigned)((a.N + RB - 1) / RB)), dim3(256), 0,
+                       a.st, a.x, a.ldx, a.W, a.ldw, a.scale, a.b, a.r, a.ldr, a.y, a.ldy, a.N, a.K, a.na);
 }
 
-template <int EPI, typename E, bool NORM, int RPW>
-void launch_r(int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const void* b, const void* r, int64_t ldr,
-              void* y, int64_t ldy, int N, int K, hipStream_t st, NormArgs<E> na) {
-    if (waves_per_row(NORM || EPI == EPI_SWIGLU || (N <= 8192 && K >= 2 * N)) == 4) launch_k<EPI, E, NORM, RPW, 4>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
-    else launch_k<EPI, E, NORM, RPW, 1>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
-}
-
-template <int EPI, typename E, bool NORM>
-void launch(int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const void* b, const void* r, int64_t ldr,
-            void* y, int64_t ldy, int N, int K, hipStream_t st, NormArgs<E> na) {
-    if constexpr (EPI == EPI_ROPE) {
-        if constexpr (NORM) launch_r<EPI, E, NORM, 2>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
-    } else if (rows_per_wave(NORM, N) == 2) {
-        launch_r<EPI, E, NORM, 2>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
+template <int EPI, bool NORM, int RPW, int KS, typename E, typename F>
+void launch_k(const Args<E, F>& a) {
+    if constexpr (EPI == EPI_ROPE) {  // one token
+        launch_m<1, EPI, NORM, RPW, KS>(a);
     } else {
-        launch_r<EPI, E, NORM, 1>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
+        switch (a.M) {
+            case 1: launch_m<1, EPI, NORM, RPW, KS>(a); break;
+            case 2: launch_m<2, EPI, NORM, RPW, KS>(a); break;
+            case 3: launch_m<3, EPI, NORM, RPW, KS>(a); break;
+            default: launch_m<4, EPI, NORM, RPW, KS>(a); break;
+        }
     }
 }
 
-template <int EPI, typename E>
-void launch_n(int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const void* b, const void* r, int64_t ldr,
-              void* y, int64_t ldy, int N, int K, hipStream_t st, const NormArgs<E>& na) {
-    if (na.g != nullptr) launch<EPI, E, true>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
-    else launch<EPI, E, false>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
+template <int EPI, bool NORM, int RPW, typename E, typename F>
+void launch_r(const Args<E, F>& a) {
+    if (waves_per_row(NORM || EPI == EPI_SWIGLU || (a.N <= 8192 && a.K >= 2 * a.N)) == 4) launch_k<EPI, NORM, RPW, 4>(a);
+    else launch_k<EPI, NORM, RPW, 1>(a);
 }
 
-template <typename E>
-void launch_epi(int epi, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const void* b, const void* r,
-                int64_t ldr, void* y, int64_t ldy, int N, int K, hipStream_t st, const NormArgs<E>& na) {
-    if (epi == EPI_ROPE) launch_n<EPI_ROPE, E>(1, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
-    else if (epi == EPI_SWIGLU) launch_n<EPI_SWIGLU, E>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
-    else if (epi == EPI_RES) launch_n<EPI_RES, E>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
-    else launch_n<EPI_NONE, E>(M, x, ldx, W, ldw, b, r, ldr, y, ldy, N, K, st, na);
+template <int EPI, bool NORM, typename E, typename F>
+void launch(const Args<E, F>& a) {
+    if constexpr (EPI == EPI_ROPE) {
+        if constexpr (NORM) launch_r<EPI, NORM, 2>(a);
+    } else if (rows_per_wave(NORM, a.N) == 2) {
+        launch_r<EPI, NORM, 2>(a);
+    } else {
+        launch_r<EPI, NORM, 1>(a);
+    }
+}
+
+template <int EPI, typename E, typename F>
+void launch_n(const Args<E, F>& a) {
+    if (a.na.g != nullptr) launch<EPI, true>(a);
+    else launch<EPI, false>(a);
+}
+
+template <typename E, typename F>
+void launch_epi(int epi, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale,
+                const void* b, const void* r, int64_t ldr, void* y, int64_t ldy, int N, int K, hipStream_t st,
+                const void* norm_w, const void* norm_add, void* norm_sum, float eps, const GemvRope& rp) {
+    const Args<E, F> a{M, (const E*)x, ldx, (const typename F::T*)W, ldw, scale, (const E*)b, (const E*)r, ldr, (E*)y,
+                       ldy, N, K, st,
+                       NormArgs<E>{(const E*)norm_w, (const E*)norm_add, (E*)norm_sum, eps, rp.cosb, rp.sinb, rp.pos,
+                                   (E*)rp.q_out, (E*)rp.kc, (E*)rp.vc, rp.nq, rp.nkv, rp.hd, rp.rd, rp.lim, rp.err}};
+    if constexpr (!F::kScaled) {
+        if (epi == EPI_ROPE) return launch_n<EPI_ROPE>(a);
+    }
+    if (epi == EPI_SWIGLU) launch_n<EPI_SWIGLU>(a);
+    else if (epi == EPI_RES) launch_n<EPI_RES>(a);
+    else launch_n<EPI_NONE>(a);
 }
 
 }  // namespace
 
 namespace sa_launch {
 // epi 0: y = x W^T (+ b); 1: y = rnd(x W^T (+ b)) + res; 2: SwiGLU over W = [gate; up] (N = F output columns);
-// 3 (with norm_w, one token): q/k/v projection + interleaved RoPE + K/V cache append (rope; y unused).
+// 3 (with norm_w, one token, dense weights): q/k/v projection + interleaved RoPE + K/V cache append (rope; y unused).
 // norm_w != nullptr: x is first replaced by rms_norm(x (+ norm_add), norm_w, eps) inside the same pass
 // (norm_add / norm_sum [M, K] contiguous; norm_sum receives x + norm_add).
-void gemv(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const void* b, void* y, int64_t ldy,
-          int N, int K, hipStream_t st, int epi, const void* res, int64_t ldr, const void* norm_w, const void* norm_add,
-          void* norm_sum, float eps, const GemvRope* rope) {
+// scale != nullptr: W holds e4m3fn codes with rows ldw bytes apart and scale one fp32 per code row ([N], [2N] for
+// epi 2); x, b, res, y, norm_* are bf16 whatever dtype says.
+void gemv(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale, const void* b,
+          void* y, int64_t ldy, int N, int K, hipStream_t st, int epi, const void* res, int64_t ldr, const void* norm_w,
+          const void* norm_add, void* norm_sum, float eps, const GemvRope* rope) {
     const GemvRope z{};
     const GemvRope& rp = rope ? *rope : z;
-    if (dtype == DT_F16) {
-        const NormArgs<_Float16> na{(const _Float16*)norm_w, (const _Float16*)norm_add, (_Float16*)norm_sum, eps,
-                                    rp.cosb, rp.sinb, rp.pos, (_Float16*)rp.q_out, (_Float16*)rp.kc, (_Float16*)rp.vc,
-                                    rp.nq, rp.nkv, rp.hd, rp.rd, rp.lim, rp.err};
-        launch_epi<_Float16>(epi, M, x, ldx, W, ldw, b, res, ldr, y, ldy, N, K, st, na);
-    } else {
-        const NormArgs<u16> na{(const u16*)norm_w, (const u16*)norm_add, (u16*)norm_sum, eps,
-                               rp.cosb, rp.sinb, rp.pos, (u16*)rp.q_out, (u16*)rp.kc, (u16*)rp.vc,
-                               rp.nq, rp.nkv, rp.hd, rp.rd, rp.lim, rp.err};
-        launch_epi<u16>(epi, M, x, ldx, W, ldw, b, res, ldr, y, ldy, N, K, st, na);
-    }
+    if (scale != nullptr)
+        launch_epi<u16, E4M3W>(epi, M, x, ldx, W, ldw, scale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps, rp);
+    else if (dtype == DT_F16)
+        launch_epi<_Float16, DenseW<_Float16>>(epi, M, x, ldx, W, ldw, scale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps, rp);
+    else
+        launch_epi<u16, DenseW<u16>>(epi, M, x, ldx, W, ldw, scale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps, rp);
 }
 }  // namespace sa_launch

@@ -161,14 +161,11 @@ struct GemvRope {
     int64_t lim; int* err;  // position bound (min(cache rows, rotary table rows)); out of range: no write, *err = 1
 };
 namespace sa_launch {
-// gemv.hip: y[M, N] = x[M, K] W[N, K]^T (+ b) for M <= 4 (decode-time linear layers), bf16 / fp16, K % 8 == 0
-void gemv(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const void* b, void* y, int64_t ldy,
-          int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
+// gemv.hip: y[M, N] = x[M, K] W[N, K]^T (+ b) for M <= 4 (decode-time linear layers), bf16 / fp16, K % 8 == 0.
+// scale != nullptr: the same layer over FP8 weights W = scale[n] * Q[n, :] (W points at Q, OCP e4m3fn codes with rows
+// ldw bytes apart; scale one fp32 power of two per code row), x / b / res / y / norm_* bf16, K % 16 == 0, epi 0 / 1 / 2
+void gemv(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale, const void* b,
+          void* y, int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
           const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
           const struct GemvRope* rope = nullptr);
-// gemv_fp8.hip: the same layer over FP8 weights W = scale[n] * Q[n, :] (Q OCP e4m3fn codes, rows ldq bytes apart,
-// scale one fp32 power of two per code row), x / b / res / y / norm_* bf16, K % 16 == 0; epi 0 / 1 / 2 as gemv()
-void gemv_w8(int M, const void* x, int64_t ldx, const void* Q, int64_t ldq, const float* scale, const void* b, void* y,
-             int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
-             const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f);
 }  // namespace sa_launch

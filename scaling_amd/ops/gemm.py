@@ -13,7 +13,7 @@ round 5).  Shapes it does not tile (M/N not multiples of 16, T not a multiple of
 
 ``linear`` is the forward ``x W^T (+ b)`` of every linear layer, ``mm_nt`` the input gradient ``dY (W^T)^T`` on
 the cached transpose and ``mm`` the input gradient ``dY W`` without it: at most 4 token rows (token-by-token decoding)
-run the weight-streaming GEMV kernel (``csrc/kernels/gemv.hip``; ``gemv_fp8.hip`` for a weight that carries a valid
+run the weight-streaming GEMV kernel (``csrc/kernels/gemv.hip``; its FP8 form for a weight that carries a valid
 FP8 copy, ``ops/quant.py``); small products (<= ``SCALING_AMD_LT_SMALL_FLOP``
 multiply-adds, 2^33 by default: none of the 7B step's) go through cached hipBLASLt plans (``csrc/blaslt.cpp``); the
 rest are plain library GEMMs (hipBLASLt through torch, TunableOp table ``scaling_amd/tuning/gemm_gfx950.csv``).  A hand-written NT GEMM with fused SwiGLU epilogues (rounds 3-5) stayed
@@ -98,7 +98,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
     no operand requiring grad); a tiny training micro-batch through a tied head keeps ``F.linear``'s backward.
 
     A weight quantised by ``ops.quant`` (``w8``: its valid FP8 copy ``(q, scale)``, looked up on ``w`` when not
-    given) streams the copy through the FP8 GEMV (``csrc/kernels/gemv_fp8.hip``) on that same branch; ``w`` holds
+    given) streams the copy through the FP8 GEMV (``csrc/kernels/gemv.hip``) on that same branch; ``w`` holds
     the dequantised values, so every other branch computes the same function."""
     K = x.shape[-1]
     rows = x.numel() // K if K else 0

@@ -1,4 +1,4 @@
-"""FP8 weight-only quantisation for token-by-token decoding (``csrc/kernels/gemv_fp8.hip``).
+"""FP8 weight-only quantisation for token-by-token decoding (the FP8 weight format of ``csrc/kernels/gemv.hip``).
 
 Scheme ``fp8_e4m3``: one output row of ``W [N, K]`` at a time.
 

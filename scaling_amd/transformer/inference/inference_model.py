@@ -103,7 +103,7 @@ class TransformerInferenceModule(InferenceModule):
         return groups, skipped
 
     def quantize_weights(self, scheme: str = "fp8_e4m3", include_lm_head: bool = False) -> dict:
-        """Opt-in FP8 weight-only decoding (``ops/quant.py``, ``csrc/kernels/gemv_fp8.hip``).
+        """Opt-in FP8 weight-only decoding (``ops/quant.py``, ``csrc/kernels/gemv.hip``).
 
         Every transformer layer's linear weights (q/k/v or fused qkv, attention dense, the MLP projections), and the
         LM head when asked (never a tied head, embeddings, norms or biases), get an OCP e4m3 copy with one

@@ -1,4 +1,4 @@
-"""FP8-weight decode GEMV (``csrc/kernels/gemv_fp8.hip``) against float math on the DEQUANTISED weights (GPU only).
+"""FP8-weight decode GEMV (the FP8 weight format of ``csrc/kernels/gemv.hip``) against float math on the DEQUANTISED weights (GPU only).
 
 The FP8 copy is an exact encoding of the bf16 values it was made from (``ops/quant.py``), so the tolerances are the
 bf16 GEMV's own -- 2e-2 against float math (``test_gemv``), 3e-2 against the bf16 kernel on the same values

@@ -1,7 +1,7 @@
 """Decode GEMV micro-benchmark on one GPU: the 7B decode projections (q/k/v, o, gate/up, down, head) at batch 1
 through the plain, epilogue-fused and norm-prologue GEMV kernels; prints us per call and the weight-stream rate.
 
-``FP8=1``: the FP8-weight kernels (``csrc/kernels/gemv_fp8.hip``) of the decode step, each right after its bf16
+``FP8=1``: the FP8-weight kernels (``csrc/kernels/gemv.hip``) of the decode step, each right after its bf16
 counterpart, in the same process, on the same shapes and under the same cold-cache protocol (``PASSES`` alternating
 passes over the list, default 2 with FP8); the rate counts the bytes each kernel streams (codes + row scales)."""
 from __future__ import annotations
