@@ -189,6 +189,35 @@ c10::optional<at::Tensor> rope_kv_append(const at::Tensor& qkv, const at::Tensor
         return c10::nullopt;
     return q;
 }
+// batched graph decode: one token of each of B sequences.  qkv [B, nq + 2 nkv, hd] (contiguous), pos [B] int64, caches
+// [B * cap, nkv, hd]: sequence b owns rows [b * cap, (b + 1) * cap) and its k/v go to row b * cap + pos[b]; returns q
+// [B, nq, hd].  Row b equals rope_kv_append on that sequence's slab bit for bit (the same kernel, blockIdx.y = b).
+c10::optional<at::Tensor> rope_kv_append_batch(const at::Tensor& qkv, const at::Tensor& cosb, const at::Tensor& sinb,
+                                               const at::Tensor& pos, int64_t nq, int64_t nkv, int64_t rot_dim,
+                                               bool interleaved, at::Tensor kc, at::Tensor vc, at::Tensor err, int64_t cap) {
+    TORCH_CHECK(err_word(err), "rope_kv_append_batch: err must be an int32 GPU tensor");
+    check_cuda(qkv, "qkv");
+    TORCH_CHECK(qkv.dim() == 3 && cap > 0, "rope_kv_append_batch: qkv must be [B, nq + 2 nkv, hd] and cap positive");
+    const int64_t B = qkv.size(0), hd = qkv.size(-1);
+    TORCH_CHECK(kc.dim() == 3 && kc.size(0) == B * cap && vc.sizes() == kc.sizes() && pos.numel() == B,
+                "rope_kv_append_batch: caches must hold B * cap rows and pos one entry per sequence");
+    if (!(B >= 1 && qkv.is_contiguous() && qkv.size(1) == nq + 2 * nkv && kc.is_contiguous() && vc.is_contiguous() &&
+          kc.size(1) == nkv && kc.size(2) == hd && kc.scalar_type() == qkv.scalar_type() &&
+          vc.scalar_type() == qkv.scalar_type() && kc.is_cuda() && vc.is_cuda() && pos.is_cuda() &&
+          pos.scalar_type() == at::kLong && pos.is_contiguous() && cosb.is_cuda() && sinb.is_cuda() &&
+          cosb.scalar_type() == at::kFloat && sinb.scalar_type() == at::kFloat && cosb.is_contiguous() &&
+          sinb.is_contiguous() && cosb.size(-1) == rot_dim / 2 && sinb.sizes() == cosb.sizes() && rot_dim <= hd &&
+          (uintptr_t)qkv.data_ptr() % 16 == 0 && (uintptr_t)kc.data_ptr() % 16 == 0 && (uintptr_t)vc.data_ptr() % 16 == 0))
+        return c10::nullopt;
+    const at::DeviceGuard g(qkv.device());
+    auto q = at::empty({B, nq, hd}, qkv.options());
+    if (!sa_launch::rope_kv_append(dt(qkv), interleaved, qkv.data_ptr(), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                                   pos.data_ptr<int64_t>(), cosb.data_ptr<float>(), sinb.data_ptr<float>(), (int)nq,
+                                   (int)nkv, (int)hd, (int)rot_dim, std::min<int64_t>(cap, cosb.size(0)),
+                                   err.data_ptr<int>(), cur_stream(), (int)B, cap))
+        return c10::nullopt;
+    return q;
+}
 
 // ------------------------------------------------------------------ cross entropy
 std::vector<at::Tensor> xent_stats(const at::Tensor& logits, const at::Tensor& target, int64_t v0) {
@@ -546,7 +575,10 @@ uint32_t drop_threshold(double p) {
 }
 std::vector<at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& cu_q,
                                const at::Tensor& cu_k, int64_t max_q, double scale, bool causal, int64_t window,
-                               double p_drop, int64_t seed, int64_t local_heads, int64_t max_k) {
+                               double p_drop, int64_t seed, int64_t local_heads, int64_t max_k,
+                               const c10::optional<at::Tensor>& k_range) {
+    // k_range: int32 [nseg, 2] = (first key row, key count) per segment, replacing cu_k (decode kernel only): the
+    // keys of a static batched cache sit in one fixed-capacity slab per sequence, not packed back to back
     check_qkv(q, "q"); check_qkv(k, "k"); check_qkv(v, "v");
     TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type(), "flash_attn: q/k/v dtypes differ");
     TORCH_CHECK(p_drop >= 0.0 && p_drop < 1.0, "flash_attn: dropout probability must be in [0, 1)");
@@ -569,12 +601,22 @@ std::vector<at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const a
     a.scale_log2 = (float)(scale * 1.4426950408889634);
     a.p_drop = (float)p_drop; a.rp_drop = (float)(1.0 / (1.0 - p_drop)); a.seed = (uint32_t)seed; a.drop_thr = drop_threshold(p_drop);
     const int64_t grp = H / k.size(1);
+    if (k_range.has_value()) {
+        TORCH_CHECK(k_range->is_cuda() && k_range->scalar_type() == at::kInt && k_range->is_contiguous() &&
+                    k_range->dim() == 2 && k_range->size(0) == a.nseg && k_range->size(1) == 2,
+                    "flash_attn: k_range must be a contiguous int32 GPU tensor [nseg, 2]");
+        TORCH_CHECK(p_drop == 0.0 && max_q * grp <= 32,
+                    "flash_attn: key ranges are supported by the decode kernel only (max_q * heads per kv head <= 32, "
+                    "no dropout)");
+        TORCH_CHECK(v.size(0) == k.size(0), "flash_attn: k and v must hold the same number of rows");
+    }
     if (T > 0 && a.nseg > 0 && p_drop == 0.0 && max_q * grp <= 32) {
         // short query segments (decode): GQA-packed rows, split-K over the keys, then a combine pass
         DecArgs d{};
         d.q = a.q; d.k = a.k; d.v = a.v;
         d.q_tok = a.q_tok; d.q_head = a.q_head; d.k_tok = a.k_tok; d.k_head = a.k_head; d.v_tok = a.v_tok; d.v_head = a.v_head;
-        d.cu_q = a.cu_q; d.cu_k = a.cu_k; d.nseg = a.nseg; d.Hq = a.Hq; d.Hkv = a.Hkv; d.causal = a.causal;
+        d.cu_q = a.cu_q; d.cu_k = a.cu_k; d.nseg = a.nseg;
+        d.k_range = k_range.has_value() ? k_range->data_ptr<int>() : nullptr; d.k_rows = k.size(0); d.Hq = a.Hq; d.Hkv = a.Hkv; d.causal = a.causal;
         d.window = a.window; d.local_heads = a.local_heads; d.scale_log2 = a.scale_log2; d.Tq = T;
         sa_launch::fa_decode_plan(max_k > 0 ? max_k : k.size(0), a.Hkv, a.nseg, d.split_keys, d.nsplit);
         auto part_o = at::empty({(int64_t)d.nsplit, T, H, D}, q.options().dtype(at::kFloat));
@@ -861,6 +903,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemm_tn", &gemm_tn, "C (+)= A^T B for k-major bf16 operands (weight-gradient GEMM)");
     m.def("rope", &rope, "rotary embedding (fwd / inverse), optional strided / in-place output", py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("rot_dim"), py::arg("seq_len"), py::arg("interleaved"), py::arg("inverse"), py::arg("out") = py::none());
     m.def("rope_kv_append", &rope_kv_append, "graph decode: RoPE q, RoPE k into the K cache row, v into the V cache row");
+    m.def("rope_kv_append_batch", &rope_kv_append_batch, "batched graph decode: rope_kv_append for one token of each of B sequences, one launch");
     m.def("xent_stats", &xent_stats, "cross-entropy row statistics");
     m.def("xent_bwd", &xent_bwd, "cross-entropy backward");
     m.def("embed_fwd", &embed_fwd, "vocab-parallel embedding forward");
@@ -882,6 +925,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("xgmi_emulate", &xgmi_emulate, "per-rank proxy: emulated collective (HBM traffic on nwg CUs, held to us)",
           py::arg("src"), py::arg("scratch"), py::arg("bytes"), py::arg("us"), py::arg("nwg") = 16);
     m.def("dropout_add", &dropout_add, "residual + dropout(x) with a hashed keep mask", py::arg("x"), py::arg("res"), py::arg("p"), py::arg("seed"));
-    m.def("fa_fwd", &fa_fwd, "flash attention forward (bf16/fp16, optional attention dropout)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("max_k") = -1);
+    m.def("fa_fwd", &fa_fwd, "flash attention forward (bf16/fp16, optional attention dropout)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("max_k") = -1, py::arg("k_range") = py::none());
     m.def("fa_bwd", &fa_bwd, "flash attention backward (optional strided dq/dk/dv outputs)", py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("max_k"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(), py::arg("dv_out") = py::none(), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("rope_cos") = py::none(), py::arg("rope_sin") = py::none(), py::arg("rope_pos") = py::none(), py::arg("rope_dim") = 0, py::arg("rope_seq") = 1, py::arg("rope_interleaved") = false);
 }

@@ -13,6 +13,8 @@
 //    O^T += V^T P^T with V^T read transposed (ds_read_b64_tr_b16) from a swizzled LDS image of the V tile.
 // Causal masking is bottom-right aligned (key <= q + Lk - Lq), sliding windows per head (local_heads) as in
 // the prefill kernels.  Rows / keys past their ranges contribute nothing.
+// A segment's keys are rows [cu_k[seg], cu_k[seg + 1]) or, with DecArgs::k_range, rows [start, start + length) of a
+// buffer that holds one fixed-capacity slab per sequence (batched decoding over a static cache).
 #include <algorithm>
 
 #include "flash_attn.h"
@@ -72,8 +74,18 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
     __shared__ __attribute__((aligned(16))) char vimg[32 * D * 2];
     constexpr int NKS = D / 16, NT = D / 32;
     const int split = blockIdx.x, hk = blockIdx.y, seg = blockIdx.z;
-    const int q0s = a.cu_q[seg], k0s = a.cu_k[seg];
-    const int Lq = a.cu_q[seg + 1] - q0s, Lk = a.cu_k[seg + 1] - k0s;
+    const int q0s = a.cu_q[seg];
+    const int Lq = a.cu_q[seg + 1] - q0s;
+    int k0s, Lk;
+    if (a.k_range) {  // (first row, count) of this segment's keys, clipped to the buffer
+        k0s = a.k_range[2 * seg];
+        Lk = a.k_range[2 * seg + 1];
+        if (k0s < 0 || Lk < 0 || k0s > a.k_rows) k0s = 0, Lk = 0;
+        Lk = (int)min((int64_t)Lk, a.k_rows - k0s);
+    } else {
+        k0s = a.cu_k[seg];
+        Lk = a.cu_k[seg + 1] - k0s;
+    }
     const int grp = a.Hq / a.Hkv;
     const int lane = threadIdx.x, h = lane >> 5, r = lane & 31;
     const int off = Lk - Lq;

@@ -27,9 +27,11 @@ void rope(int dtype, bool interleaved, const void* x, int64_t x_tok, int64_t x_h
           int seq_len, float sign, hipStream_t st);
 // graph decode: RoPE(q) -> q_out, RoPE(k) -> K cache row *pos, v -> V cache row *pos (one token); false = unsupported
 // lim = min(cache rows, rotary table rows); a position outside [0, lim) writes nothing but zeros into q and sets *err
+// B > 1: one token of each of B sequences (x [B][nq + 2 nkv][hd], pos [B], q_out [B][nq][hd]); sequence b owns cache
+// rows [b * cap, (b + 1) * cap) and writes row b * cap + pos[b]; lim = min(cap, rotary table rows), per sequence
 bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, void* kc, void* vc, const int64_t* pos,
                     const float* cosb, const float* sinb, int nq, int nkv, int hd, int rd, int64_t lim, int* err,
-                    hipStream_t st);
+                    hipStream_t st, int B = 1, int64_t cap = 0);
 }  // namespace sa_launch
 
 namespace sa_launch {
@@ -81,6 +83,9 @@ struct DecArgs {
     const uint16_t* q; const uint16_t* k; const uint16_t* v;
     int64_t q_tok, q_head, k_tok, k_head, v_tok, v_head;
     const int* cu_q; const int* cu_k;
+    // optional [nseg][2] = (first key row, key count) per segment: replaces cu_k for keys that are not packed back
+    // to back (one fixed-capacity slab per sequence); k_rows = rows of the key buffer, ranges are clipped to it
+    const int* k_range; int64_t k_rows;
     int nseg, Hq, Hkv, causal, window, local_heads;
     float scale_log2;
     int split_keys, nsplit;

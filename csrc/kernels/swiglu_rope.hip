@@ -155,23 +155,28 @@ __global__ __launch_bounds__(256) void rope_kernel(const T* __restrict__ x, T* _
     }
 }
 
-// Graph-decode step (one token): RoPE of the q and k heads and the K/V cache append in ONE launch.  x is the QKV
-// projection row [nq + 2 nkv heads][hd] (contiguous); q heads are rotated into q_out [nq][hd]; k heads are rotated
-// straight into row *pos of the K cache and v heads copied into row *pos of the V cache ([cap][nkv][hd] each) --
-// replacing rope(q), rope(k) and two index_copy launches.  One work item = 8 pair slots (as rope_v8_kernel).
-// lim = min(cache rows, rotary table rows): a position outside [0, lim) writes no cache row, zeros q and sets *err
-// (the caller checks the word on the host; an out-of-range row index would otherwise write past the cache silently).
+// Graph-decode step (one token per sequence): RoPE of the q and k heads and the K/V cache append in ONE launch.  x is
+// the QKV projection [B][nq + 2 nkv heads][hd] (contiguous), blockIdx.y = b the sequence; q heads are rotated into
+// q_out [b][nq][hd]; k heads are rotated straight into row b * cap + pos[b] of the K cache and v heads copied into the
+// same row of the V cache ([B * cap][nkv][hd] each: one slab of cap rows per sequence; B = 1 is the one-sequence
+// cache) -- replacing rope(q), rope(k) and two index_copy launches.  One work item = 8 pair slots (as rope_v8_kernel).
+// lim = min(cap, rotary table rows): a sequence whose position is outside [0, lim) writes no cache row, zeros its own
+// q row and sets *err (the caller checks the word on the host; an out-of-range row index would otherwise write past
+// its slab silently); the other sequences are unaffected.
 template <typename T, bool IL>
 __global__ __launch_bounds__(256) void rope_kv_append_kernel(const T* __restrict__ x, T* __restrict__ q_out,
                                                              T* __restrict__ kc, T* __restrict__ vc,
                                                              const int64_t* __restrict__ pos, const float* cosb,
                                                              const float* sinb, int nq, int nkv, int hd, int rd,
-                                                             int64_t lim, int* __restrict__ err) {
+                                                             int64_t lim, int64_t cap, int* __restrict__ err) {
     const int half = rd / 2;
     const int rc = IL ? rd / 8 : half / 8;
     const int CR = rc + (hd - rd) / 8;
     const int nh = nq + 2 * nkv;
-    const int64_t ps = pos[0];
+    const int b = blockIdx.y;
+    const int64_t ps = pos[b];
+    x += (int64_t)b * nh * hd;
+    q_out += (int64_t)b * nq * hd;
     if (ps < 0 || ps >= lim) {
         if (blockIdx.x == 0 && threadIdx.x == 0) *err = 1;
         for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nq * hd / 8; i += gridDim.x * blockDim.x) {
@@ -186,8 +191,8 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(const T* __restrict
         const T* xr = x + (int64_t)h * hd;
         T* orow;
         if (h < nq) orow = q_out + (int64_t)h * hd;
-        else if (h < nq + nkv) orow = kc + (ps * nkv + (h - nq)) * hd;
-        else orow = vc + (ps * nkv + (h - nq - nkv)) * hd;
+        else if (h < nq + nkv) orow = kc + ((b * cap + ps) * nkv + (h - nq)) * hd;
+        else orow = vc + ((b * cap + ps) * nkv + (h - nq - nkv)) * hd;
         if (h >= nq + nkv) {  // v: plain copy of the row's chunks
             for (int e = 8 * c; e < hd; e += 8 * CR) {
                 float v[8];
@@ -241,13 +246,13 @@ static int grid_for(int64_t n) {
 namespace sa_launch {
 bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, void* kc, void* vc, const int64_t* pos,
                     const float* cosb, const float* sinb, int nq, int nkv, int hd, int rd, int64_t lim, int* err,
-                    hipStream_t st) {
-    if (dtype == DT_F32 || hd % 8 || (interleaved ? rd % 8 : rd % 16)) return false;
+                    hipStream_t st, int B, int64_t cap) {
+    if (dtype == DT_F32 || hd % 8 || (interleaved ? rd % 8 : rd % 16) || B < 1 || B > 65535) return false;
     const int CR = (interleaved ? rd / 8 : rd / 16) + (hd - rd) / 8;
-    const int g = grid_for((int64_t)(nq + 2 * nkv) * CR);
+    const dim3 g(grid_for((int64_t)(nq + 2 * nkv) * CR), B);
 #define SA_RKV(TT, IL)                                                                                            \
     hipLaunchKernelGGL((rope_kv_append_kernel<TT, IL>), g, 256, 0, st, (const TT*)x, (TT*)q_out, (TT*)kc, (TT*)vc, \
-                       pos, cosb, sinb, nq, nkv, hd, rd, lim, err)
+                       pos, cosb, sinb, nq, nkv, hd, rd, lim, cap, err)
     if (dtype == DT_BF16) { if (interleaved) SA_RKV(u16, true); else SA_RKV(u16, false); }
     else { if (interleaved) SA_RKV(f16, true); else SA_RKV(f16, false); }
 #undef SA_RKV

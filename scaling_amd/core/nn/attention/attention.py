@@ -17,7 +17,7 @@ from __future__ import annotations
 import math
 import os
 from enum import Enum
-from typing import Any, Callable, Optional, Union
+from typing import Any, Callable, Optional, Sequence, Union
 
 import torch
 
@@ -223,6 +223,81 @@ class StaticKVCache:
         self.k.index_copy_(0, self.state.pos, k)
         self.v.index_copy_(0, self.state.pos, v)
         return self.k, self.v, self.state.cu_k
+
+
+class BatchDecodeState:
+    """``DecodeState`` for B sequences of different lengths decoded together: ``pos`` [B] int64 is each sequence's
+    position (the row inside its cache slab) of the token being fed, ``k_range`` [B, 2] int32 = (b * cap, pos[b] + 1)
+    the key rows the flash-decoding kernel reads for sequence b, ``err`` one shared error word.  ``reset``,
+    ``advance`` and ``check`` run device ops only (``check`` ends in one host read)."""
+
+    def __init__(self, prompt_lengths: Sequence[int], capacity: int, device: torch.device) -> None:
+        n = len(prompt_lengths)
+        assert n >= 1 and capacity >= 1 and n * capacity < 2**31, (n, capacity)
+        self.batch, self.capacity = n, capacity
+        self.pos = torch.zeros(n, dtype=torch.long, device=device)
+        self.row_base = torch.arange(n, dtype=torch.long, device=device) * capacity
+        self.k_range = torch.zeros(n, 2, dtype=torch.int32, device=device)
+        self.k_range[:, 0].copy_(self.row_base)
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self.reset(prompt_lengths)
+
+    def reset(self, prompt_lengths: Union[Sequence[int], torch.Tensor]) -> None:
+        if not isinstance(prompt_lengths, torch.Tensor):  # a device tensor is copied without a host round trip
+            prompt_lengths = torch.tensor(list(prompt_lengths), dtype=torch.long)
+        assert prompt_lengths.numel() == self.batch
+        self.pos.copy_(prompt_lengths)
+        self.k_range[:, 1].copy_(self.pos)
+        self.k_range[:, 1].add_(1)
+        self.err.zero_()
+
+    def check(self) -> None:
+        """Raises if a decode step ran a sequence at a position outside its slab or the rotary table."""
+        if int(self.err.item()) != 0:
+            raise RuntimeError("batched decode: a sequence's position exceeded its static KV cache slab or the rotary "
+                               "table; its K/V rows were not written")
+
+    def advance(self) -> None:
+        self.pos.add_(1)
+        self.k_range[:, 1].add_(1)
+
+
+class BatchStaticKVCache:
+    """``StaticKVCache`` for B sequences: ``[B * cap, nkv, hd]`` buffers in which sequence b owns the slab of rows
+    [b * cap, (b + 1) * cap) -- fixed addresses whatever the lengths, so a captured step has constant pointers and
+    shapes.  A step writes sequence b's new row at ``b * cap + pos[b]`` and attention reads ``state.k_range``."""
+
+    def __init__(self, k: torch.Tensor, v: torch.Tensor, state: BatchDecodeState) -> None:
+        assert k.shape[0] == state.batch * state.capacity, (tuple(k.shape), state.batch, state.capacity)
+        self.k, self.v, self.state = k, v, state
+
+    @classmethod
+    def from_caches(cls, kvs: Sequence["KVCache"], state: BatchDecodeState) -> "BatchStaticKVCache":
+        """From the per-prompt caches the prefills left (sequence b's first ``kvs[b].length`` rows are copied)."""
+        cap = state.capacity
+        assert len(kvs) == state.batch
+        k0 = kvs[0].k
+        kb = k0.new_zeros((len(kvs) * cap,) + tuple(k0.shape[1:]))
+        vb = torch.zeros_like(kb)
+        for b, kv in enumerate(kvs):
+            n = kv.length
+            assert n <= cap, (n, cap)
+            kb[b * cap : b * cap + n].copy_(kv.k[:n])
+            vb[b * cap : b * cap + n].copy_(kv.v[:n])
+        return cls(kb, vb, state)
+
+    def append(self, k: torch.Tensor, v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The unfused write of one token per sequence (``k``, ``v`` [B, nkv, hd]); a position outside the slab
+        rewrites the row it is clamped to with that row's own content and sets the error word."""
+        st = self.state
+        assert k.shape[0] == st.batch, "batched decoding feeds one token per sequence and step"
+        bad = (st.pos < 0) | (st.pos >= st.capacity)
+        rows = st.row_base + st.pos.clamp(0, st.capacity - 1)
+        keep = bad.view(-1, 1, 1)
+        self.k.index_copy_(0, rows, torch.where(keep, self.k.index_select(0, rows), k))
+        self.v.index_copy_(0, rows, torch.where(keep, self.v.index_select(0, rows), v))
+        st.err.bitwise_or_(bad.any().to(torch.int32))
+        return self.k, self.v, st.k_range
 
 
 class _LoraUpInto(torch.autograd.Function):
@@ -564,6 +639,8 @@ class ParallelSelfAttention(torch.nn.Module):
         the cache position tensor; None otherwise (the caller runs the unfused ops)."""
         kv = self.cache.get(cache_index)
         re = self.rotary_embedding
+        if isinstance(kv, BatchStaticKVCache):
+            return self._decode_rope_append_batch(kv, base, q, k, v, position_ids)
         if not (isinstance(kv, StaticKVCache) and re is not None and self.use_flash_attention and use_native(base)):
             return None
         if position_ids is None or position_ids.numel() != 1 or position_ids.data_ptr() != kv.state.pos.data_ptr():
@@ -579,6 +656,31 @@ class ParallelSelfAttention(torch.nn.Module):
         if qr is None:
             return None
         return qr, kv.k, kv.v, kv.state.cu_k
+
+    def _decode_rope_append_batch(self, kv: BatchStaticKVCache, base: torch.Tensor, q: torch.Tensor, k: torch.Tensor,
+                                  v: torch.Tensor, position_ids: Optional[torch.Tensor]) -> Optional[tuple]:
+        """``_decode_rope_append`` for one token of each of the B sequences of a batched static cache, still ONE launch
+        (``ext().rope_kv_append_batch``): row b is rotated at ``pos[b]`` and appended to slab b.  The fourth entry of
+        the result is the cache's key ranges, not cu_seqlens."""
+        re = self.rotary_embedding
+        st = kv.state
+        if not (re is not None and self.use_flash_attention and use_native(base)):
+            return None
+        if position_ids is None or position_ids.numel() != st.batch or position_ids.data_ptr() != st.pos.data_ptr():
+            return None
+        hd, nq, nkv = self.hidden_size_per_attention_head, q.shape[1], k.shape[1]
+        nh = nq + 2 * nkv
+        es = base.element_size()
+        if not (base.is_contiguous() and base.numel() == st.batch * nh * hd and q.shape[0] == st.batch
+                and q.data_ptr() == base.data_ptr() and k.data_ptr() == base.data_ptr() + nq * hd * es
+                and v.data_ptr() == base.data_ptr() + (nq + nkv) * hd * es
+                and all(t.stride(1) == hd and (st.batch == 1 or t.stride(0) == nh * hd) for t in (q, k, v))):
+            return None
+        qr = ext().rope_kv_append_batch(base.view(st.batch, nh, hd), re.cos_table, re.sin_table, st.pos, nq, nkv,
+                                        re.dimensions, re.interleaved, kv.k, kv.v, st.err, st.capacity)
+        if qr is None:
+            return None
+        return qr, kv.k, kv.v, st.k_range
 
     # ------------------------------------------------------------------ forward
     def forward(
@@ -605,6 +707,10 @@ class ParallelSelfAttention(torch.nn.Module):
         T = b * s
         hd = self.hidden_size_per_attention_head
         fused_append: Optional[tuple] = None
+        # batched decoding (BatchStaticKVCache): one token of each of b sequences, keys read by (start, length) ranges
+        batch_kv = self.cache.get(cache_index) if use_cache and not reset_cache else None
+        if not isinstance(batch_kv, BatchStaticKVCache):
+            batch_kv = None
         probe("attention.input", x)
         if projected_step is not None:  # graph decode: norm + q/k/v GEMV + RoPE + K/V append were one launch
             q, k, v, cumulative_seq_lengths_key = projected_step
@@ -631,7 +737,8 @@ class ParallelSelfAttention(torch.nn.Module):
                 assert self.norm_query is not None and self.norm_key is not None
                 q = all_shard(self.norm_query(all_concat(q, dim=1, topology=self.topology)), dim=1, topology=self.topology)
                 k = all_shard(self.norm_key(all_concat(k, dim=1, topology=self.topology)), dim=1, topology=self.topology)
-            if use_cache and not reset_cache and T == 1 and not self.key_query_norm and _DECODE_FUSED:
+            if (use_cache and not reset_cache and (T == 1 or batch_kv is not None) and not self.key_query_norm
+                    and _DECODE_FUSED):
                 fused_append = self._decode_rope_append(base, q, k, v, position_ids, cache_index)
             if fused_append is not None:  # graph decode: RoPE + K/V cache append in one launch
                 q, k, v, cumulative_seq_lengths_key = fused_append
@@ -643,9 +750,13 @@ class ParallelSelfAttention(torch.nn.Module):
         if use_cache and fused_append is None:
             if not self.causal:
                 raise ValueError("KV caching is only supported for causal attention.")
-            assert b == 1, f"KV caching is only supported for batch size 1, got {b}"
+            assert b == 1 or batch_kv is not None, f"KV caching is only supported for batch size 1, got {b}"
             kv = None if reset_cache else self.cache[cache_index]
-            if isinstance(kv, StaticKVCache):  # graph-captured decoding: device-side write index and key range
+            if batch_kv is not None:  # one token per sequence at row_base + pos (unfused: CPU, key_query_norm, fp32)
+                assert self.use_flash_attention, "batched decoding needs the flash attention kernel"
+                assert s == 1 and b == batch_kv.state.batch, "batched decoding feeds one token per sequence"
+                k, v, cumulative_seq_lengths_key = batch_kv.append(k, v)
+            elif isinstance(kv, StaticKVCache):  # graph-captured decoding: device-side write index and key range
                 assert self.use_flash_attention, "graph-captured decoding needs the flash attention kernel"
                 k, v, cumulative_seq_lengths_key = kv.append(k, v)
             else:
@@ -673,6 +784,10 @@ class ParallelSelfAttention(torch.nn.Module):
             # mixed local/global heads: ONE launch, the kernel picks the window per q head (heads [0, nl)
             # windowed) — no second launch, no repeat_kv (reference attention.py:619-667 runs two)
             window = self.local_attention_window_size if nl > 0 else None
+            if batch_kv is not None:  # keys by (start, length); the split plan is sized by one sequence's capacity
+                assert s == 1 and b == batch_kv.state.batch, "batched decoding feeds one token per sequence"
+                common.update(cu_seqlens_k=None, key_ranges=cumulative_seq_lengths_key,
+                              max_seqlen_k=batch_kv.state.capacity)
             hidden = attn_ops.flash_attention(q, k, v, window=window, **common,
                                               local_heads=self.num_local_attention_heads_per_partition if nl > 0 else None)
             hidden = hidden.reshape(b, s, -1)

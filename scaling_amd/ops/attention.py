@@ -72,16 +72,25 @@ def dropout_seed(device: torch.device) -> int:
 
 
 def attention_reference(q, k, v, cu_q, cu_k, scale, causal, window=-1, dropout_p: float = 0.0, training=False,
-                        dropout_seed_value: Optional[int] = None, local_heads: Optional[int] = None):
+                        dropout_seed_value: Optional[int] = None, local_heads: Optional[int] = None,
+                        key_ranges: Optional[torch.Tensor] = None):
     """Dense per-segment fp32 attention (numerical oracle and CPU path). q:[T,Hq,D], k/v:[Tk,Hk,D].
     With ``dropout_seed_value`` the dropout mask is the fused kernel's (:func:`dropout_keep_mask`).
-    ``local_heads``: only q heads [0, local_heads) use ``window``, the others attend globally."""
+    ``local_heads``: only q heads [0, local_heads) use ``window``, the others attend globally.
+    ``key_ranges`` [nseg, 2] = (first key row, key count): segment i reads keys [start, start + count) instead of
+    [cu_k[i], cu_k[i + 1]) (``cu_k`` is then unused and may be None); rows outside the ranges are never read."""
     Hq, Hk = q.shape[1], k.shape[1]
     rep = Hq // Hk
     out = torch.empty(q.shape[0], Hq, v.shape[2], dtype=q.dtype, device=q.device)
-    cq, ck = cu_q.tolist(), cu_k.tolist()
+    cq = cu_q.tolist()
+    if key_ranges is not None:
+        assert tuple(key_ranges.shape) == (len(cq) - 1, 2), "key_ranges must be [nseg, 2]"
+        spans = [(int(s0), int(s0) + int(n)) for s0, n in key_ranges.tolist()]
+    else:
+        ck = cu_k.tolist()
+        spans = list(zip(ck[:-1], ck[1:]))
     for i in range(len(cq) - 1):
-        qs, qe, ks, ke = cq[i], cq[i + 1], ck[i], ck[i + 1]
+        qs, qe, (ks, ke) = cq[i], cq[i + 1], spans[i]
         if qe == qs:
             continue
         qi = q[qs:qe].float().transpose(0, 1)  # [H, Lq, D]
@@ -297,6 +306,34 @@ def rope_flash_attention(base: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v
                                 float(dropout_p), seed, -1 if local_heads is None else int(local_heads))
 
 
+def _flash_attention_ranges(q, k, v, cu_seqlens_q, key_ranges, max_seqlen_q, max_seqlen_k, softmax_scale, causal,
+                            window, p_drop, local_heads) -> torch.Tensor:
+    """:func:`flash_attention` with ``key_ranges``: the flash-decoding kernel, or the dense reference on CPU."""
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    win = -1 if window is None else int(window)
+    if p_drop > 0.0:
+        raise ValueError("flash attention: key_ranges do not support dropout")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise ValueError("flash attention: key_ranges are forward only (run under torch.no_grad())")
+    if not use_native(q):
+        return attention_reference(q, k, v, cu_seqlens_q, None, scale, causal, win, local_heads=local_heads,
+                                   key_ranges=key_ranges)
+    if q.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError(f"flash attention supports bfloat16 / float16 inputs, got {q.dtype}")
+    if max_seqlen_k is None:
+        raise ValueError("flash attention: key_ranges need max_seqlen_k (the per-sequence capacity)")
+    cq = cu_seqlens_q.to(torch.int32)
+    if max_seqlen_q is None:
+        max_seqlen_q = int((cq[1:] - cq[:-1]).max().item())
+    if int(max_seqlen_q) * (q.shape[1] // k.shape[1]) > 32:
+        raise ValueError("flash attention: key_ranges are supported by the decode kernel only "
+                         "(max_seqlen_q * q heads per kv head <= 32)")
+    lh = -1 if local_heads is None else int(local_heads)
+    o, _ = ext().fa_fwd(q, k, v, cq, cq, int(max_seqlen_q), float(scale), bool(causal), win, 0.0, 0, lh,
+                        int(max_seqlen_k), key_ranges)
+    return o
+
+
 def flash_attention(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -312,11 +349,21 @@ def flash_attention(
     training: bool = False,
     local_heads: Optional[int] = None,
     deterministic: bool = True,
+    key_ranges: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """q: [T, Hq, D]; k, v: [Tk, Hk, D] (unit last stride); cu_seqlens int32 [nseg+1].
 
     ``local_heads``: with a ``window``, only q heads [0, local_heads) are windowed and the rest attend
-    globally — mixed local/global heads in ONE launch (the kernels pick the window per head)."""
+    globally — mixed local/global heads in ONE launch (the kernels pick the window per head).
+
+    ``key_ranges`` int32 [nseg, 2] = (first key row, key count): segment i reads keys [start, start + count) of k / v
+    instead of [cu_seqlens_k[i], cu_seqlens_k[i + 1]) -- a batched static KV cache keeps one fixed-capacity slab per
+    sequence, so the keys are not packed back to back.  ``cu_seqlens_k`` is then ignored and ``max_seqlen_k`` (the
+    per-sequence capacity; it sizes the split plan) is required.  Decode-sized calls only (max_seqlen_q * q heads per
+    kv head <= 32, no dropout), forward only: anything else raises."""
+    if key_ranges is not None:
+        return _flash_attention_ranges(q, k, v, cu_seqlens_q, key_ranges, max_seqlen_q, max_seqlen_k, softmax_scale,
+                                       causal, window, dropout_p if training else 0.0, local_heads)
     if cu_seqlens_k is None:
         cu_seqlens_k = cu_seqlens_q
         max_seqlen_k = max_seqlen_q

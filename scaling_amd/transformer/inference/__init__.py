@@ -1,7 +1,9 @@
+from .batch_decode import BatchDecoder
 from .inference_model import CompletionOutput, TransformerInferenceModule
 from .sample import Sampler, fast_multinomial, sample_argmax, sample_temperature, top_k_transform, top_p_transform
 
 __all__ = [
+    "BatchDecoder",
     "CompletionOutput",
     "Sampler",
     "TransformerInferenceModule",

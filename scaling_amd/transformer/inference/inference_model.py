@@ -224,6 +224,77 @@ class TransformerInferenceModule(InferenceModule):
         text = self.tokenizer.decode(tokens) if self.tokenizer is not None else None
         return CompletionOutput(completion_text=text, completion_tokens=tokens, completion_logits=logits)
 
+    def batch_decoder(self, max_tokens: int, input_tokens: Sequence[Sequence[int]],
+                      sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax) -> Any:
+        """Prefills the prompts one at a time (prompt b under ``cache_index`` b), draws every row's first token with
+        ONE ``sample_fn`` call on the stacked prefill logits and returns the ``batch_decode.BatchDecoder`` that decodes
+        them together (not yet captured: call ``capture()`` for graph replay)."""
+        from .batch_decode import BatchDecoder
+
+        if len(input_tokens) == 0:
+            raise ValueError("generate_batch: no prompts")
+        if any(len(p) == 0 for p in input_tokens):
+            raise ValueError("generate_batch: empty prompt")
+        if max_tokens < 1:
+            raise ValueError("generate_batch: max_tokens must be at least 1")
+        if self.devices is None or len(self.devices) != 1:
+            raise RuntimeError("generate_batch: the model must sit on one device")
+        if hasattr(sample_fn, "reset"):
+            sample_fn.reset(0)
+        last = []
+        for b, toks in enumerate(input_tokens):
+            settings = InferenceSettings(use_cache=True, reset_cache=True, cache_index=b, embedding_layers=[-1])
+            out = self.forward(TextDatasetBatch(input_token_ids=torch.tensor(list(toks)).unsqueeze(0),
+                                                inference_settings=settings))
+            last.append(out.activations[:, -1, :])
+        prefill = torch.stack(last)  # [B, 1, V]
+        first = sample_fn(prefill)
+        return BatchDecoder(self, [len(p) for p in input_tokens], max_tokens, first, sample_fn, prefill)
+
+    def generate_batch(self, max_tokens: int, input_texts: Optional[Sequence[str]] = None,
+                       input_tokens: Optional[Sequence[Sequence[int]]] = None,
+                       sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
+                       stop_tokens: Optional[Sequence[int]] = None,
+                       use_cuda_graph: bool = False) -> list[CompletionOutput]:
+        """Completions for B prompts of any lengths, decoded together: one pass over the weights per step serves all
+        B rows (``batch_decode.BatchDecoder``).  One device, always with the KV cache (flash attention kernel); the
+        prompts are prefilled one at a time.  Stop tokens act per row: every row keeps stepping until all rows have
+        stopped or ``max_tokens`` is reached, and each row's completion is cut at its first stop token.
+
+        Greedy completions equal ``generate``'s per prompt up to the rounding of the batched kernels.  With a seeded
+        ``sample.Sampler`` the row index is part of every draw, so a sampled batch does not repeat the text each
+        prompt gets alone.
+
+        ``use_cuda_graph`` replays the step as one HIP graph and needs ``B <= ops.gemm.GEMV_MAX_ROWS`` (4): above 4
+        rows ``ops.gemm.linear`` uses a cached hipBLASLt plan in eager mode but torch's own path under capture, and
+        the two need not pick the same algorithm, so graph tokens could not be kept equal to eager tokens.  The eager
+        loop takes any B (rows > 4 run the library GEMMs and the unfused norm / SwiGLU kernels)."""
+        from ...ops.gemm import GEMV_MAX_ROWS
+
+        if (input_texts is None) == (input_tokens is None):
+            raise ValueError("generate_batch: give either input_texts or input_tokens")
+        if input_texts is not None:
+            assert self.tokenizer is not None
+            input_tokens = [self.tokenizer.encode(t) for t in input_texts]
+        assert input_tokens is not None
+        if use_cuda_graph and len(input_tokens) > GEMV_MAX_ROWS:
+            raise ValueError(
+                f"generate_batch: use_cuda_graph supports at most {GEMV_MAX_ROWS} prompts, got {len(input_tokens)}: "
+                "above that the linear layers use a cached hipBLASLt plan in eager mode but torch's own GEMM path "
+                "under graph capture, which need not pick the same algorithm, so graph tokens could differ from "
+                "eager tokens; run without use_cuda_graph")
+        if stop_tokens is None:
+            assert self.tokenizer is not None, "If no tokenizer is provided, a stop token needs to be set manually"
+            stop_tokens = [self.tokenizer.eos_token_id]
+        dec = self.batch_decoder(max_tokens, input_tokens, sample_fn)
+        if use_cuda_graph:
+            dec.capture()
+        outs = []
+        for tokens, logits in dec.run(stop_tokens):
+            text = self.tokenizer.decode(tokens) if self.tokenizer is not None else None
+            outs.append(CompletionOutput(completion_text=text, completion_tokens=tokens, completion_logits=logits))
+        return outs
+
     def _generate_graph(self, prompt: TextDatasetBatch, n_in: int, max_tokens: int,
                         sample_fn: Callable[[torch.Tensor], torch.Tensor], stop_tokens: Sequence[int]) -> CompletionOutput:
         from .graph_decode import GraphDecoder

@@ -1,7 +1,11 @@
 """Batch-1 decode latency on one GPU: eager cached generation vs HIP-graph-captured decoding, greedy or sampled.
 
     python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64] [--sampler T,K,P | torch:T,K,P]
-                                 [--weights fp8_e4m3 [--lm-head]]
+                                 [--weights fp8_e4m3 [--lm-head]] [--batch B]
+
+``--batch B`` times batched generation instead (``generate_batch`` / ``BatchDecoder``): B random prompts of lengths
+``prompt, prompt - 7, prompt - 14, ...`` decoded together; ms per step, tokens/s summed over the rows, and (B <= 4:
+the graph limit) the captured loop and ``graph_tokens_equal_eager``.
 
 ``--weights fp8_e4m3`` decodes the model after ``quantize_weights()`` (FP8 weight-only decoding; ``--lm-head`` includes
 the LM head); ``weights_gib`` and ``graph_gb_per_s`` then count what one decode step streams (the FP8 copies in place of
@@ -37,6 +41,7 @@ def main() -> None:
     p.add_argument("--sampler", default=None, help="T,K,P: fused Sampler; torch:T,K,P: torch composition (eager only)")
     p.add_argument("--weights", default="bf16", choices=["bf16", "fp8_e4m3"], help="fp8_e4m3: quantize_weights() first")
     p.add_argument("--lm-head", action="store_true", help="with --weights fp8_e4m3: quantise the LM head too")
+    p.add_argument("--batch", type=int, default=0, help="B >= 1: time batched generation of B prompts")
     a = p.parse_args()
     from scaling_amd.models import llama_architecture
     from scaling_amd.transformer.context.config import TransformerArchitectureConfig
@@ -78,6 +83,12 @@ def main() -> None:
         torch.cuda.synchronize()
         return time.perf_counter() - t, r
 
+    if a.batch >= 1:
+        if not graph_ok:
+            raise SystemExit("--batch needs a graph-safe sampler (greedy or T,K,P)")
+        batch_bench(m, a, arch, sample_fn, mode, timed, quantised)
+        return
+
     m.generate(4, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn)  # warm-up (library handles, tables)
     t1, _ = timed(lambda: m.generate(1, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn))
     tn, eager = timed(lambda: m.generate(a.tokens + 1, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn))
@@ -113,6 +124,34 @@ def main() -> None:
         "graph_tokens_equal_eager": same, "weights_gib": round(weights / 2**30, 2),
         "graph_gb_per_s": round(weights / (graph_ms * 1e-3) / 1e9, 1), **extra,
     }), flush=True)
+
+
+def batch_bench(m, a, arch, sample_fn, mode, timed, quantised) -> None:
+    """``--batch B``: per-step time of the batched decode loop (prefills and capture excluded)."""
+    from scaling_amd.ops.gemm import GEMV_MAX_ROWS
+
+    B, steps = a.batch, a.tokens
+    prompts = [torch.randint(1, arch.vocab_size, (max(1, a.prompt - 7 * b),)).tolist() for b in range(B)]
+    m.generate_batch(4, input_tokens=prompts, stop_tokens=[], sample_fn=sample_fn)  # warm-up
+    dec = m.batch_decoder(steps + 1, prompts, sample_fn)
+    te, eager = timed(lambda: dec.run([], check_every=steps + 1))
+    eager_ms = 1000.0 * te / steps
+    weights = sum(p.numel() * p.element_size() for p in m.parameters())
+    if quantised is not None:
+        weights = weights - quantised["bf16_bytes"] + quantised["fp8_bytes"]
+    res = {"metric": "batched decode ms/step", "batch": B, "sampler": mode, "model": a.model, "layers": arch.num_layers,
+           "prompt": a.prompt, "tokens": steps, "weights": a.weights, "eager_ms_per_step": round(eager_ms, 3),
+           "eager_tokens_per_s": round(B * 1000.0 / eager_ms, 1), "weights_gib": round(weights / 2**30, 2)}
+    if B <= GEMV_MAX_ROWS:
+        dec = m.batch_decoder(steps + 1, prompts, sample_fn)
+        tc, _ = timed(dec.capture)
+        tg, graph = timed(lambda: dec.run([], check_every=steps + 1))
+        graph_ms = 1000.0 * tg / steps
+        res.update(graph_ms_per_step=round(graph_ms, 3), graph_tokens_per_s=round(B * 1000.0 / graph_ms, 1),
+                   graph_capture_ms=round(1000.0 * tc, 1),
+                   graph_tokens_equal_eager=[g[0] for g in graph] == [e[0] for e in eager],
+                   graph_gb_per_s=round(weights / (graph_ms * 1e-3) / 1e9, 1))
+    print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":
