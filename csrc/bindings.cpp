@@ -373,7 +373,10 @@ at::Tensor transpose2d(const at::Tensor& x) {
 //    as uint8), scale [N] fp32 powers of two (ops/quant.py); x bf16.  16-byte pieces of 16 codes: K % 16 == 0, Q rows
 //    a multiple of 16 bytes apart, 16-byte aligned bases.
 // Each pair of bound functions is one worker; name is the bound function's, for the error messages.
-bool gemv_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale) {
+// The skinny* names are the same layers on the MFMA kernel (skinny.hip): the same operand rules with M <= 16 (skinny
+// = true below), the same signatures and return conventions; there is no RoPE form.
+constexpr int64_t kGemvRows = 4, kSkinnyRows = 16;
+bool gemv_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale, bool skinny = false) {
     const int64_t P = scale ? 16 : 8;  // weights per 16-byte piece
     if (!(x.is_cuda() && W.is_cuda() && x.dim() == 2 && W.dim() == 2)) return false;
     if (scale) {
@@ -388,23 +391,35 @@ bool gemv_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor
     } else if (x.scalar_type() != W.scalar_type() || (x.scalar_type() != at::kBFloat16 && x.scalar_type() != at::kHalf)) {
         return false;
     }
-    if (x.size(0) < 1 || x.size(0) > 4 || x.size(1) != W.size(1) || x.size(1) % P != 0 || W.size(0) < 1) return false;
+    if (x.size(0) < 1 || x.size(0) > (skinny ? kSkinnyRows : kGemvRows) || x.size(1) != W.size(1) || x.size(1) % P != 0 || W.size(0) < 1) return false;
     if (x.stride(1) != 1 || W.stride(1) != 1 || (x.size(0) > 1 && x.stride(0) % 8 != 0) || W.stride(0) % P != 0)
         return false;
     return (uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)W.data_ptr() % 16 == 0;
 }
-bool gemv_norm_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale, const at::Tensor& gamma) {
-    if (!gemv_operands_ok(x, W, scale) || !x.is_contiguous()) return false;
+bool gemv_norm_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale, const at::Tensor& gamma,
+                           bool skinny = false) {
+    if (!gemv_operands_ok(x, W, scale, skinny) || !x.is_contiguous()) return false;
     return gamma.is_cuda() && gamma.dim() == 1 && gamma.numel() == x.size(1) && gamma.is_contiguous() &&
            gamma.scalar_type() == x.scalar_type() && (uintptr_t)gamma.data_ptr() % 16 == 0;
 }
 const float* scale_ptr(const at::Tensor* scale) { return scale ? scale->data_ptr<float>() : nullptr; }
+// one launcher for both kernels (epi 3, the RoPE step, is gemv's alone and launched where it is bound)
+void gemv_launch(bool skinny, int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale,
+                 const void* b, void* y, int64_t ldy, int N, int K, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
+                 const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f) {
+    if (skinny)
+        sa_launch::skinny(dtype, M, x, ldx, W, ldw, scale, b, y, ldy, N, K, cur_stream(), epi, res, ldr, norm_w, norm_add,
+                          norm_sum, eps);
+    else
+        sa_launch::gemv(dtype, M, x, ldx, W, ldw, scale, b, y, ldy, N, K, cur_stream(), epi, res, ldr, norm_w, norm_add,
+                        norm_sum, eps);
+}
 
 at::Tensor gemv_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
-                     const c10::optional<at::Tensor>& bias) {
-    TORCH_CHECK(gemv_operands_ok(x, W, scale), name, ": unsupported operands ",
-                scale ? "(x bf16 [M<=4, K], Q e4m3fn [N, K], scale fp32 [N], K % 16 == 0, 16-byte aligned rows)"
-                      : "(x [M<=4, K], W [N, K], bf16/fp16, K % 8 == 0, aligned)");
+                     const c10::optional<at::Tensor>& bias, bool skinny = false) {
+    TORCH_CHECK(gemv_operands_ok(x, W, scale, skinny), name, ": unsupported operands ",
+                scale ? "(x bf16 [M, K], Q e4m3fn [N, K], scale fp32 [N], K % 16 == 0, 16-byte aligned rows"
+                      : "(x [M, K], W [N, K], bf16/fp16, K % 8 == 0, aligned", skinny ? ", M <= 16)" : ", M <= 4)");
     const at::DeviceGuard g(x.device());
     const int64_t M = x.size(0), N = W.size(0), K = W.size(1);
     const void* bp = nullptr;
@@ -415,32 +430,33 @@ at::Tensor gemv_impl(const char* name, const at::Tensor& x, const at::Tensor& W,
         bp = bc.data_ptr();
     }
     auto y = at::empty({M, N}, x.options());
-    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), bp, y.data_ptr(), N,
-                    (int)N, (int)K, cur_stream());
+    gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), bp,
+                y.data_ptr(), N, (int)N, (int)K);
     return y;
 }
 // decode epilogues: y = rnd(x W^T) + res  (res [M, N]) ...
 at::Tensor gemv_residual_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
-                              const at::Tensor& res) {
-    TORCH_CHECK(gemv_operands_ok(x, W, scale), name, ": unsupported operands");
+                              const at::Tensor& res, bool skinny = false) {
+    TORCH_CHECK(gemv_operands_ok(x, W, scale, skinny), name, ": unsupported operands");
     const int64_t M = x.size(0), N = W.size(0), K = W.size(1);
     TORCH_CHECK(res.is_cuda() && res.dim() == 2 && res.size(0) == M && res.size(1) == N && res.stride(1) == 1 &&
                     res.scalar_type() == x.scalar_type(), name, ": res must be [M, N] of the input dtype");
     const at::DeviceGuard g(x.device());
     auto y = at::empty({M, N}, x.options());
-    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
-                    y.data_ptr(), N, (int)N, (int)K, cur_stream(), 1, res.data_ptr(), res.stride(0));
+    gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
+                y.data_ptr(), N, (int)N, (int)K, 1, res.data_ptr(), res.stride(0));
     return y;
 }
 // ... and SwiGLU over W = [gate; up] ([2F, K]): y[:, n] = silu(x W_gate^T)[n] * (x W_up^T)[n], rounded as gemv + swiglu
 // (FP8: scale [2F], the halves keep their own row scales)
-at::Tensor gemv_swiglu_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale) {
-    TORCH_CHECK(gemv_operands_ok(x, W, scale) && W.size(0) % 2 == 0, name, ": unsupported operands");
+at::Tensor gemv_swiglu_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
+                            bool skinny = false) {
+    TORCH_CHECK(gemv_operands_ok(x, W, scale, skinny) && W.size(0) % 2 == 0, name, ": unsupported operands");
     const int64_t M = x.size(0), F = W.size(0) / 2, K = W.size(1);
     const at::DeviceGuard g(x.device());
     auto y = at::empty({M, F}, x.options());
-    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
-                    y.data_ptr(), F, (int)F, (int)K, cur_stream(), 2, nullptr, 0);
+    gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
+                y.data_ptr(), F, (int)F, (int)K, 2, nullptr, 0);
     return y;
 }
 // ... with the RMSNorm in front fused into the same pass: s = x (+ add); y = gemv(rms_norm(s, gamma, eps), W) with
@@ -448,8 +464,8 @@ at::Tensor gemv_swiglu_impl(const char* name, const at::Tensor& x, const at::Ten
 // kernel when add is given
 std::vector<at::Tensor> gemv_norm_impl(const char* name, const at::Tensor& x, const c10::optional<at::Tensor>& add,
                                        const at::Tensor& gamma, double eps, const at::Tensor& W, const at::Tensor* scale,
-                                       int64_t epi) {
-    TORCH_CHECK(gemv_norm_operands_ok(x, W, scale, gamma) && (epi == 0 || (epi == 2 && W.size(0) % 2 == 0)), name,
+                                       int64_t epi, bool skinny = false) {
+    TORCH_CHECK(gemv_norm_operands_ok(x, W, scale, gamma, skinny) && (epi == 0 || (epi == 2 && W.size(0) % 2 == 0)), name,
                 ": unsupported operands");
     const int64_t M = x.size(0), K = W.size(1), N = epi == 2 ? W.size(0) / 2 : W.size(0);
     const at::DeviceGuard g(x.device());
@@ -463,9 +479,9 @@ std::vector<at::Tensor> gemv_norm_impl(const char* name, const at::Tensor& x, co
         ap = add->data_ptr();
     }
     auto y = at::empty({M, N}, x.options());
-    sa_launch::gemv(dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
-                    y.data_ptr(), N, (int)N, (int)K, cur_stream(), (int)epi, nullptr, 0, gamma.data_ptr(), ap,
-                    ap ? s.data_ptr() : nullptr, (float)eps);
+    gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
+                y.data_ptr(), N, (int)N, (int)K, (int)epi, nullptr, 0, gamma.data_ptr(), ap, ap ? s.data_ptr() : nullptr,
+                (float)eps);
     return {s, y};
 }
 
@@ -500,6 +516,40 @@ bool gemv_w8_norm_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor&
 std::vector<at::Tensor> gemv_w8_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
                                      double eps, const at::Tensor& Q, const at::Tensor& scale, int64_t epi) {
     return gemv_norm_impl("gemv_w8_norm", x, add, gamma, eps, Q, &scale, epi);
+}
+
+// the same twelve entry points on the MFMA kernel, M <= 16 (skinny.hip)
+bool skinny_ok(const at::Tensor& x, const at::Tensor& W) { return gemv_operands_ok(x, W, nullptr, true); }
+at::Tensor skinny(const at::Tensor& x, const at::Tensor& W, c10::optional<at::Tensor> bias) {
+    return gemv_impl("skinny", x, W, nullptr, bias, true);
+}
+at::Tensor skinny_residual(const at::Tensor& x, const at::Tensor& W, const at::Tensor& res) {
+    return gemv_residual_impl("skinny_residual", x, W, nullptr, res, true);
+}
+at::Tensor skinny_swiglu(const at::Tensor& x, const at::Tensor& W) { return gemv_swiglu_impl("skinny_swiglu", x, W, nullptr, true); }
+bool skinny_norm_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor& gamma) {
+    return gemv_norm_operands_ok(x, W, nullptr, gamma, true);
+}
+std::vector<at::Tensor> skinny_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
+                                    double eps, const at::Tensor& W, int64_t epi) {
+    return gemv_norm_impl("skinny_norm", x, add, gamma, eps, W, nullptr, epi, true);
+}
+bool skinny_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) { return gemv_operands_ok(x, Q, &scale, true); }
+at::Tensor skinny_w8(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, c10::optional<at::Tensor> bias) {
+    return gemv_impl("skinny_w8", x, Q, &scale, bias, true);
+}
+at::Tensor skinny_w8_residual(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& res) {
+    return gemv_residual_impl("skinny_w8_residual", x, Q, &scale, res, true);
+}
+at::Tensor skinny_w8_swiglu(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    return gemv_swiglu_impl("skinny_w8_swiglu", x, Q, &scale, true);
+}
+bool skinny_w8_norm_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& gamma) {
+    return gemv_norm_operands_ok(x, Q, &scale, gamma, true);
+}
+std::vector<at::Tensor> skinny_w8_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
+                                       double eps, const at::Tensor& Q, const at::Tensor& scale, int64_t epi) {
+    return gemv_norm_impl("skinny_w8_norm", x, add, gamma, eps, Q, &scale, epi, true);
 }
 
 // graph-decode q/k/v step in ONE launch: q = RoPE(rms_norm(x) Wq^T) is returned, RoPE(rms_norm(x) Wk^T) and
@@ -899,6 +949,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "in one launch; returns q or None");
     m.def("gemv_norm", &gemv_norm, "(s, gemv(rms_norm(s), W)) with s = x (+ add); epi 0 plain, 2 SwiGLU (decode)",
           py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("W"), py::arg("epi") = 0);
+    m.def("skinny_ok", &skinny_ok, "whether skinny supports these operands");
+    m.def("skinny", &skinny, "y = x W^T (+ b) for at most 16 rows of x on the MFMA weight-streaming kernel (batched decode)",
+          py::arg("x"), py::arg("W"), py::arg("bias") = py::none());
+    m.def("skinny_residual", &skinny_residual, "y = x W^T + res for at most 16 rows (decode down / o-projection + residual)");
+    m.def("skinny_swiglu", &skinny_swiglu, "y = silu(x Wg^T) * (x Wu^T) for W = [Wg; Wu], at most 16 rows (decode)");
+    m.def("skinny_norm_ok", &skinny_norm_ok, "whether skinny_norm supports these operands");
+    m.def("skinny_norm", &skinny_norm, "(s, skinny(rms_norm(s), W)) with s = x (+ add); epi 0 plain, 2 SwiGLU (decode)",
+          py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("W"), py::arg("epi") = 0);
+    m.def("skinny_w8_ok", &skinny_w8_ok, "whether the FP8-weight skinny kernel supports these operands");
+    m.def("skinny_w8", &skinny_w8, "y = x (scale * Q)^T (+ b) for at most 16 bf16 rows of x, Q e4m3fn codes, scale fp32 per row",
+          py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("bias") = py::none());
+    m.def("skinny_w8_residual", &skinny_w8_residual, "skinny_w8 + res (decode down / o-projection + residual)");
+    m.def("skinny_w8_swiglu", &skinny_w8_swiglu, "silu(x Wg^T) * (x Wu^T) over FP8 [Wg; Wu] with per-row scales (decode)");
+    m.def("skinny_w8_norm_ok", &skinny_w8_norm_ok, "whether skinny_w8_norm supports these operands");
+    m.def("skinny_w8_norm", &skinny_w8_norm, "(s, skinny_w8(rms_norm(s), Q, scale)) with s = x (+ add); epi 0 plain, 2 SwiGLU",
+          py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("q"), py::arg("scale"), py::arg("epi") = 0);
     m.def("gemm_tn_ok", &gemm_tn_ok, "whether gemm_tn supports these operands");
     m.def("gemm_tn", &gemm_tn, "C (+)= A^T B for k-major bf16 operands (weight-gradient GEMM)");
     m.def("rope", &rope, "rotary embedding (fwd / inverse), optional strided / in-place output", py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("rot_dim"), py::arg("seq_len"), py::arg("interleaved"), py::arg("inverse"), py::arg("out") = py::none());

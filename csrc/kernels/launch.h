@@ -173,4 +173,11 @@ void gemv(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t l
           void* y, int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
           const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
           const struct GemvRope* rope = nullptr);
+// skinny.hip: the same layer for M <= 16 rows on the matrix cores (16x16x32 MFMA, weight tile as A, x as B); the
+// arguments, weight formats and epilogues of gemv (epi 0 / 1 / 2, the NORM prologue; no RoPE form).  The launch rules
+// depend on N, K, the format and the form, never on M: row m of y is bitwise the same for every M and whatever the
+// other rows hold.  Rows >= M of x / norm_add / res are never read.
+void skinny(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale, const void* b,
+            void* y, int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
+            const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f);
 }  // namespace sa_launch

@@ -23,6 +23,7 @@ import torch
 
 from ....ops import attention as attn_ops
 from ....ops._ext import ext, use_native
+from ....ops.gemm import decode_kernel, decode_rows_limit
 from ...topology import Topology
 from ..linear import ColumnParallelLinear, RowParallelLinear
 from ..linear.fused import fused_column_linear
@@ -496,8 +497,8 @@ class ParallelSelfAttention(torch.nn.Module):
 
     def decode_norm_project(self, x: torch.Tensor, norm: torch.nn.Module, position_ids: Optional[torch.Tensor] = None,
                             use_cache: bool = False, reset_cache: bool = False, cache_index: int = 0) -> Optional[dict]:
-        """The q/k/v projection of ``norm(x)`` for decode-sized inputs (<= 4 tokens, no autograd graph, bias-free,
-        no pending LoRA) as ONE GEMV launch that folds the RMSNorm into its pass over the weights
+        """The q/k/v projection of ``norm(x)`` for decode-sized inputs (<= 4 tokens, <= 16 inside
+        ``ops.gemm.skinny_gemm()``; no autograd graph, bias-free, no pending LoRA) as ONE GEMV launch that folds the RMSNorm into its pass over the weights
         (``ext().gemv_norm``; the normalised row stays fp32).  Returns the keyword arguments to pass to ``forward``:
         ``projected_base`` (the projection), or -- graph-captured decoding of one token with interleaved RoPE --
         ``projected_step`` (q rotated, k rotated and v already appended to the static cache by the same launch,
@@ -511,7 +512,7 @@ class ParallelSelfAttention(torch.nn.Module):
             return None
         K = x.shape[-1]
         rows = x.numel() // K if K else 0
-        if not 0 < rows <= 4:
+        if not 0 < rows <= decode_rows_limit():
             return None
         if self.lora_config is not None and not self.lora_merged_state:
             return None
@@ -523,18 +524,18 @@ class ParallelSelfAttention(torch.nn.Module):
             return None
         w = weights[0] if len(weights) == 1 else adjacent_weights(weights)
         x2 = x.reshape(rows, K)
-        if w is None or not ext().gemv_norm_ok(x2, w, nw[0]):
+        if w is None or not decode_kernel(rows, "_norm_ok")(x2, w, nw[0]):
             return None
         w8 = adjacent_w8(weights)
-        if w8 is not None and ext().gemv_w8_norm_ok(x2, w8[0], w8[1], nw[0]):
+        if w8 is not None and decode_kernel(rows, "_w8_norm_ok")(x2, w8[0], w8[1], nw[0]):
             # quantised weights (ops/quant.py): the FP8 GEMV with the norm folded in; the one-launch RoPE step has no
             # FP8 form, so RoPE + K/V append follow as their own launch (_decode_rope_append)
-            _, base = ext().gemv_w8_norm(x2, None, nw[0], nw[1], w8[0], w8[1], 0)
+            _, base = decode_kernel(rows, "_w8_norm")(x2, None, nw[0], nw[1], w8[0], w8[1], 0)
             return {"projected_base": base.view(*x.shape[:-1], w.shape[0])}
         step = self._decode_norm_rope_step(x2, nw, w, position_ids, use_cache, reset_cache, cache_index)
         if step is not None:
             return {"projected_step": step}
-        _, base = ext().gemv_norm(x2, None, nw[0], nw[1], w, 0)
+        _, base = decode_kernel(rows, "_norm")(x2, None, nw[0], nw[1], w, 0)
         return {"projected_base": base.view(*x.shape[:-1], w.shape[0])}
 
     def _decode_norm_rope_step(self, x2: torch.Tensor, nw: tuple, w: torch.Tensor, position_ids: Optional[torch.Tensor],

@@ -51,7 +51,7 @@ import torch.distributed as dist
 
 from ....ops.attention import stash_gemm
 from ....ops.gemm import linear as gemm_linear
-from ....ops.gemm import GEMV_MAX_ROWS, mm, mm_nt, transpose2d, wgrad
+from ....ops.gemm import decode_rows_limit, mm, mm_nt, transpose2d, wgrad
 from ....ops.quant import adjacent_w8 as _adjacent_w8
 from ...utils.debug_env import side_streams_enabled
 
@@ -245,7 +245,7 @@ class _MultiLinear(torch.autograd.Function):
             b = biases[0] if n == 1 else torch.cat(biases, dim=0)  # type: ignore[arg-type]
         # decode-sized rows of quantised weights stream the FP8 copy (w itself may be a fresh view over the group)
         K = x.shape[-1]
-        w8 = adjacent_w8(weights) if K and 0 < x.numel() // K <= GEMV_MAX_ROWS else None  # type: ignore[arg-type]
+        w8 = adjacent_w8(weights) if K and 0 < x.numel() // K <= decode_rows_limit() else None  # type: ignore[arg-type]
         out = stash_gemm(lambda: gemm_linear(x, w, b, w8=w8))
         wt = _transposed(weights, w) if want_wt else None
         ctx.has_wt = wt is not None

@@ -17,6 +17,7 @@ import torch
 
 from ...ops import swiglu as swiglu_ops
 from ...ops._ext import ext, use_native
+from ...ops.gemm import decode_kernel, decode_rows_limit
 from ..topology import Topology
 from .activation_function import ActivationFunction, get_activation_function
 from .linear import ColumnParallelLinear, RowParallelLinear
@@ -95,11 +96,12 @@ class ParallelSwiGLUMLP(torch.nn.Module):
         )
 
     def _decode_weights(self, x: torch.Tensor, residual: torch.Tensor) -> Optional[tuple[torch.Tensor, torch.Tensor]]:
-        """``([gate; up], down)`` weights for the decode GEMV path (<= 4 rows, no autograd graph, TP 1, bias-free,
+        """``([gate; up], down)`` weights for the decode GEMV path (<= ``ops.gemm.decode_rows_limit()`` rows: 4, or 16 on the MFMA
+        kernel inside ``ops.gemm.skinny_gemm()``; no autograd graph, TP 1, bias-free,
         GEMV-compatible layouts), None when it does not apply."""
         K = x.shape[-1]
         rows = x.numel() // K if K else 0
-        if not (0 < rows <= 4 and use_native(x) and residual.shape == x.shape[:-1] + (self.dense_out.out_features,)):
+        if not (0 < rows <= decode_rows_limit() and use_native(x) and residual.shape == x.shape[:-1] + (self.dense_out.out_features,)):
             return None
         if self.topology is not None and self.topology.config.model_parallel_size > 1:
             return None
@@ -110,7 +112,7 @@ class ParallelSwiGLUMLP(torch.nn.Module):
             return None
         w = adjacent_weights([self.dense_in.weight, self.siglu_weight.weight])
         wo = self.dense_out.weight
-        if (w is None or not ext().gemv_ok(x.reshape(rows, K), w) or wo.dtype != w.dtype or wo.stride(1) != 1
+        if (w is None or not decode_kernel(rows, "_ok")(x.reshape(rows, K), w) or wo.dtype != w.dtype or wo.stride(1) != 1
                 or wo.stride(0) % 8 or wo.shape[1] != w.shape[0] // 2 or wo.shape[1] % 8 or wo.data_ptr() % 16):
             return None
         return w, wo
@@ -122,9 +124,10 @@ class ParallelSwiGLUMLP(torch.nn.Module):
 
     @staticmethod
     def _down_residual(a: torch.Tensor, wo: torch.Tensor, wo8: Optional[tuple], res: torch.Tensor) -> torch.Tensor:
-        if wo8 is not None and ext().gemv_w8_ok(a, wo8[0], wo8[1]):
-            return ext().gemv_w8_residual(a, wo8[0], wo8[1], res)
-        return ext().gemv_residual(a, wo, res)
+        rows = a.shape[0]
+        if wo8 is not None and decode_kernel(rows, "_w8_ok")(a, wo8[0], wo8[1]):
+            return decode_kernel(rows, "_w8_residual")(a, wo8[0], wo8[1], res)
+        return decode_kernel(rows, "_residual")(a, wo, res)
 
     def decode_forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> Optional[torch.Tensor]:
         """``residual + self(x)`` for decode-sized inputs (<= 4 tokens, no autograd graph, TP 1, bias-free) as two
@@ -136,10 +139,10 @@ class ParallelSwiGLUMLP(torch.nn.Module):
         rows = x.numel() // x.shape[-1]
         x2 = x.reshape(rows, -1)
         w8, wo8 = self._decode_w8()
-        if w8 is not None and ext().gemv_w8_ok(x2, w8[0], w8[1]):
-            h = ext().gemv_w8_swiglu(x2, w8[0], w8[1])
+        if w8 is not None and decode_kernel(rows, "_w8_ok")(x2, w8[0], w8[1]):
+            h = decode_kernel(rows, "_w8_swiglu")(x2, w8[0], w8[1])
         else:
-            h = ext().gemv_swiglu(x2, ws[0])
+            h = decode_kernel(rows, "_swiglu")(x2, ws[0])
         return self._down_residual(h, ws[1], wo8, residual.reshape(rows, -1)).view(residual.shape)
 
     def decode_forward_norm(self, h: torch.Tensor, residual: torch.Tensor, norm: torch.nn.Module) -> Optional[torch.Tensor]:
@@ -158,13 +161,13 @@ class ParallelSwiGLUMLP(torch.nn.Module):
             return None
         rows = h.numel() // h.shape[-1]
         h2 = h.reshape(rows, -1)
-        if not ext().gemv_norm_ok(h2, ws[0], nw[0]):
+        if not decode_kernel(rows, "_norm_ok")(h2, ws[0], nw[0]):
             return None
         w8, wo8 = self._decode_w8()
-        if w8 is not None and ext().gemv_w8_norm_ok(h2, w8[0], w8[1], nw[0]):
-            s, a = ext().gemv_w8_norm(h2, residual.reshape(rows, -1), nw[0], nw[1], w8[0], w8[1], 2)
+        if w8 is not None and decode_kernel(rows, "_w8_norm_ok")(h2, w8[0], w8[1], nw[0]):
+            s, a = decode_kernel(rows, "_w8_norm")(h2, residual.reshape(rows, -1), nw[0], nw[1], w8[0], w8[1], 2)
         else:
-            s, a = ext().gemv_norm(h2, residual.reshape(rows, -1), nw[0], nw[1], ws[0], 2)
+            s, a = decode_kernel(rows, "_norm")(h2, residual.reshape(rows, -1), nw[0], nw[1], ws[0], 2)
         return self._down_residual(a, ws[1], wo8, s).view(residual.shape)
 
     def forward(self, x: torch.Tensor, sp_shard: bool = False) -> torch.Tensor:

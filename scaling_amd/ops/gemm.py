@@ -14,7 +14,9 @@ round 5).  Shapes it does not tile (M/N not multiples of 16, T not a multiple of
 ``linear`` is the forward ``x W^T (+ b)`` of every linear layer, ``mm_nt`` the input gradient ``dY (W^T)^T`` on
 the cached transpose and ``mm`` the input gradient ``dY W`` without it: at most 4 token rows (token-by-token decoding)
 run the weight-streaming GEMV kernel (``csrc/kernels/gemv.hip``; its FP8 form for a weight that carries a valid
-FP8 copy, ``ops/quant.py``); small products (<= ``SCALING_AMD_LT_SMALL_FLOP``
+FP8 copy, ``ops/quant.py``); inside ``skinny_gemm()`` (opt-in, batched decoding) ``SKINNY_MIN_ROWS`` to 16 rows run
+the MFMA weight-streaming kernel (``csrc/kernels/skinny.hip``: the same forms and weight formats, a time that does
+not grow with the row count, and row m of its result bitwise independent of the other rows); small products (<= ``SCALING_AMD_LT_SMALL_FLOP``
 multiply-adds, 2^33 by default: none of the 7B step's) go through cached hipBLASLt plans (``csrc/blaslt.cpp``); the
 rest are plain library GEMMs (hipBLASLt through torch, TunableOp table ``scaling_amd/tuning/gemm_gfx950.csv``).  A hand-written NT GEMM with fused SwiGLU epilogues (rounds 3-5) stayed
 1-6 % behind hipBLASLt at every 7B shape and lost in the step even with its epilogues
@@ -22,8 +24,9 @@ rest are plain library GEMMs (hipBLASLt through torch, TunableOp table ``scaling
 """
 from __future__ import annotations
 
+import contextlib
 import os
-from typing import Optional
+from typing import Callable, Iterator, Optional
 
 import torch
 
@@ -58,6 +61,42 @@ def transpose2d(x: torch.Tensor) -> torch.Tensor:
 
 
 GEMV_MAX_ROWS = 4
+SKINNY_MAX_ROWS = 16
+# the smallest row count that takes the MFMA kernel inside skinny_gemm(): from 3 rows on it is at least as fast as the
+# GEMV on all five 7B shapes, bf16 and FP8; at 2 rows it loses on o, gate/up and the head (profiles/gemv_skinny_bench.log;
+# the B = 2 step: 4.33 ms against the GEMV's 3.50, profiles/decode_skinny_ab_min2.jsonl); one and two rows stay on the GEMV
+SKINNY_MIN_ROWS = 3
+_skinny = False
+
+
+@contextlib.contextmanager
+def skinny_gemm(enabled: bool = True) -> Iterator[None]:
+    """Inside, decode-sized linear layers of ``SKINNY_MIN_ROWS`` to ``SKINNY_MAX_ROWS`` rows run the MFMA kernel
+    (``ext().skinny*``) and ``decode_rows_limit()`` is 16.  Nestable; the previous state is restored on exit and on an
+    exception.  Outside nothing changes."""
+    global _skinny
+    prev = _skinny
+    _skinny = bool(enabled)
+    try:
+        yield
+    finally:
+        _skinny = prev
+
+
+def decode_rows_limit() -> int:
+    """The most rows the fused decode paths (weight-streaming kernels + epilogues) take: 4, or 16 inside ``skinny_gemm()``."""
+    return SKINNY_MAX_ROWS if _skinny else GEMV_MAX_ROWS
+
+
+def use_skinny(rows: int) -> bool:
+    """Whether ``rows`` decode rows run the MFMA kernel (else the GEMV, which takes at most ``GEMV_MAX_ROWS``)."""
+    return _skinny and (rows >= SKINNY_MIN_ROWS or rows > GEMV_MAX_ROWS) and rows <= SKINNY_MAX_ROWS
+
+
+def decode_kernel(rows: int, suffix: str = "") -> Callable:
+    """``ext().gemv<suffix>`` or, where ``use_skinny(rows)``, ``ext().skinny<suffix>``: the two kernels bind the same
+    names with the same signatures (``_ok``, ``_residual``, ``_swiglu``, ``_norm``, ``_w8...``)."""
+    return getattr(ext(), ("skinny" if use_skinny(rows) else "gemv") + suffix)
 # products of at most this many multiply-adds go through cached hipBLASLt plans (csrc/blaslt.cpp): torch's path
 # re-plans every call (~25-30 us of host time), which only a host-bound small model notices; 0 disables
 _LT_SMALL = int(os.environ.get("SCALING_AMD_LT_SMALL_FLOP", str(1 << 33)))
@@ -92,7 +131,8 @@ def mm_nt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
            w8: Optional[tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
-    """``F.linear(x, w, b)``; decode-sized inputs (<= 4 rows) on the GEMV kernel.
+    """``F.linear(x, w, b)``; decode-sized inputs (<= 4 rows) on the GEMV kernel, inside ``skinny_gemm()``
+    ``SKINNY_MIN_ROWS`` to 16 rows on the MFMA kernel under the same conditions.
 
     The GEMV kernel is a raw op without autograd, so it only serves calls that build no graph (grad mode off, or
     no operand requiring grad); a tiny training micro-batch through a tied head keeps ``F.linear``'s backward.
@@ -105,12 +145,12 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
     needs_graph = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad))
     if w8 is None and getattr(w, "_sa_w8", None) is not None:
         w8 = w8_of(w)  # (drops a stale copy, whichever branch serves this call)
-    if 0 < rows <= GEMV_MAX_ROWS and not needs_graph and use_native(x) and w.dim() == 2:
+    if 0 < rows <= decode_rows_limit() and not needs_graph and use_native(x) and w.dim() == 2:
         x2 = x.reshape(rows, K)
-        if w8 is not None and ext().gemv_w8_ok(x2, w8[0], w8[1]) and (b is None or b.dtype == x.dtype):
-            return ext().gemv_w8(x2, w8[0], w8[1], b).reshape(*x.shape[:-1], w.shape[0])
-        if ext().gemv_ok(x2, w) and (b is None or b.dtype == w.dtype):
-            return ext().gemv(x2, w, b).reshape(*x.shape[:-1], w.shape[0])
+        if w8 is not None and decode_kernel(rows, "_w8_ok")(x2, w8[0], w8[1]) and (b is None or b.dtype == x.dtype):
+            return decode_kernel(rows, "_w8")(x2, w8[0], w8[1], b).reshape(*x.shape[:-1], w.shape[0])
+        if decode_kernel(rows, "_ok")(x2, w) and (b is None or b.dtype == w.dtype):
+            return decode_kernel(rows)(x2, w, b).reshape(*x.shape[:-1], w.shape[0])
     if not needs_graph and w.dim() == 2 and _lt_ok(x, w, rows, w.shape[0], K) and (b is None or b.dtype == w.dtype):
         # (written into the un-flattened output: a view of a 2-D result would not be updatable in place -- the
         # in-base LoRA up-projections accumulate into the q/k/v GEMM output)

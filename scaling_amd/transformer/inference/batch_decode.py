@@ -16,6 +16,12 @@ library GEMMs and the unfused norm / SwiGLU kernels.  Graph capture is limited t
 ``ops.gemm.linear`` uses a cached hipBLASLt plan in eager mode but torch's own path under capture, and the two need
 not pick the same algorithm, so graph tokens could differ from eager tokens.
 
+``skinny_gemm=True`` (opt-in) runs every step -- eager, warm-up and capture alike -- inside
+``ops.gemm.skinny_gemm()``: ``ops.gemm.SKINNY_MIN_ROWS`` to 16 rows then take the MFMA weight-streaming kernels
+(``csrc/kernels/skinny.hip``, bf16 / fp16 or FP8 copies, the same fused epilogues), whose time does not grow with the
+row count and whose rows do not depend on each other, and the graph limit becomes 16 rows.  Above 16 rows the eager
+loop runs the library path as without the flag.
+
 Sampling: the first token of all rows is ONE ``sample_fn`` call on the stacked ``[B, 1, V]`` prefill logits (step 0,
 rows 0..B-1) and every later step is one call on the step's ``[B, 1, V]`` logits.  ``sample.Sampler`` hashes
 ``(seed, step, row)``, and the row index is part of the draw: a sampled batch does NOT repeat the text each prompt
@@ -27,6 +33,7 @@ from typing import Any, Callable, Optional, Sequence
 
 import torch
 
+from ...ops import gemm as gemm_ops
 from ...core.nn.attention.attention import BatchDecodeState, BatchStaticKVCache, KVCache, ParallelSelfAttention
 from ..data import TextDatasetBatch
 from ..data.inference_settings import InferenceSettings
@@ -41,8 +48,10 @@ class BatchDecoder:
     prefill's."""
 
     def __init__(self, module: Any, prompt_lengths: Sequence[int], max_tokens: int, first_tokens: torch.Tensor,
-                 sample_fn: Callable[[torch.Tensor], torch.Tensor], prefill_logits: torch.Tensor) -> None:
+                 sample_fn: Callable[[torch.Tensor], torch.Tensor], prefill_logits: torch.Tensor,
+                 skinny_gemm: bool = False) -> None:
         self.module = module
+        self.skinny_gemm = bool(skinny_gemm)
         dev = first_tokens.device
         B = len(prompt_lengths)
         assert B >= 1 and max_tokens >= 1 and first_tokens.numel() == B and prefill_logits.shape[0] == B
@@ -82,7 +91,8 @@ class BatchDecoder:
     def _step(self) -> None:
         """One decode step, device ops only: feed ``tok`` at ``pos``, sample into ``tok``, record, advance."""
         B = self.batch_size
-        out = self.module.forward(self.batch)
+        with gemm_ops.skinny_gemm(self.skinny_gemm):
+            out = self.module.forward(self.batch)
         act = out.activations
         nxt = self.sample_fn(act).reshape(B, 1)
         self.tok.copy_(nxt)

@@ -225,10 +225,12 @@ class TransformerInferenceModule(InferenceModule):
         return CompletionOutput(completion_text=text, completion_tokens=tokens, completion_logits=logits)
 
     def batch_decoder(self, max_tokens: int, input_tokens: Sequence[Sequence[int]],
-                      sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax) -> Any:
+                      sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
+                      skinny_gemm: bool = False) -> Any:
         """Prefills the prompts one at a time (prompt b under ``cache_index`` b), draws every row's first token with
         ONE ``sample_fn`` call on the stacked prefill logits and returns the ``batch_decode.BatchDecoder`` that decodes
-        them together (not yet captured: call ``capture()`` for graph replay)."""
+        them together (not yet captured: call ``capture()`` for graph replay).  ``skinny_gemm``: its steps run inside
+        ``ops.gemm.skinny_gemm()`` (the MFMA weight-streaming kernels for up to 16 rows, see ``generate_batch``)."""
         from .batch_decode import BatchDecoder
 
         if len(input_tokens) == 0:
@@ -249,13 +251,14 @@ class TransformerInferenceModule(InferenceModule):
             last.append(out.activations[:, -1, :])
         prefill = torch.stack(last)  # [B, 1, V]
         first = sample_fn(prefill)
-        return BatchDecoder(self, [len(p) for p in input_tokens], max_tokens, first, sample_fn, prefill)
+        return BatchDecoder(self, [len(p) for p in input_tokens], max_tokens, first, sample_fn, prefill,
+                            skinny_gemm=skinny_gemm)
 
     def generate_batch(self, max_tokens: int, input_texts: Optional[Sequence[str]] = None,
                        input_tokens: Optional[Sequence[Sequence[int]]] = None,
                        sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                        stop_tokens: Optional[Sequence[int]] = None,
-                       use_cuda_graph: bool = False) -> list[CompletionOutput]:
+                       use_cuda_graph: bool = False, skinny_gemm: bool = False) -> list[CompletionOutput]:
         """Completions for B prompts of any lengths, decoded together: one pass over the weights per step serves all
         B rows (``batch_decode.BatchDecoder``).  One device, always with the KV cache (flash attention kernel); the
         prompts are prefilled one at a time.  Stop tokens act per row: every row keeps stepping until all rows have
@@ -268,8 +271,14 @@ class TransformerInferenceModule(InferenceModule):
         ``use_cuda_graph`` replays the step as one HIP graph and needs ``B <= ops.gemm.GEMV_MAX_ROWS`` (4): above 4
         rows ``ops.gemm.linear`` uses a cached hipBLASLt plan in eager mode but torch's own path under capture, and
         the two need not pick the same algorithm, so graph tokens could not be kept equal to eager tokens.  The eager
-        loop takes any B (rows > 4 run the library GEMMs and the unfused norm / SwiGLU kernels)."""
-        from ...ops.gemm import GEMV_MAX_ROWS
+        loop takes any B (rows > 4 run the library GEMMs and the unfused norm / SwiGLU kernels).
+
+        ``skinny_gemm`` (opt-in) decodes ``ops.gemm.SKINNY_MIN_ROWS <= B <= 16`` rows on the MFMA weight-streaming
+        kernels (``csrc/kernels/skinny.hip``; ``ops.gemm.skinny_gemm``), eager and graph alike, under the conditions of
+        the GEMV paths (bf16 / fp16 model, optionally FP8 copies, one device, TP 1); ``use_cuda_graph`` then takes up to
+        16 prompts.  Every row of those kernels is bitwise independent of the other rows.  The flag is inert off the
+        GPU, and above 16 rows the eager loop runs the library path as without it."""
+        from ...ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS
 
         if (input_texts is None) == (input_tokens is None):
             raise ValueError("generate_batch: give either input_texts or input_tokens")
@@ -277,7 +286,12 @@ class TransformerInferenceModule(InferenceModule):
             assert self.tokenizer is not None
             input_tokens = [self.tokenizer.encode(t) for t in input_texts]
         assert input_tokens is not None
-        if use_cuda_graph and len(input_tokens) > GEMV_MAX_ROWS:
+        if use_cuda_graph and skinny_gemm and len(input_tokens) > SKINNY_MAX_ROWS:
+            raise ValueError(
+                f"generate_batch: use_cuda_graph with skinny_gemm supports at most {SKINNY_MAX_ROWS} prompts, got "
+                f"{len(input_tokens)}: above that the linear layers run library GEMMs, whose algorithm choice under "
+                "graph capture need not be the eager one; run without use_cuda_graph")
+        if use_cuda_graph and not skinny_gemm and len(input_tokens) > GEMV_MAX_ROWS:
             raise ValueError(
                 f"generate_batch: use_cuda_graph supports at most {GEMV_MAX_ROWS} prompts, got {len(input_tokens)}: "
                 "above that the linear layers use a cached hipBLASLt plan in eager mode but torch's own GEMM path "
@@ -286,7 +300,7 @@ class TransformerInferenceModule(InferenceModule):
         if stop_tokens is None:
             assert self.tokenizer is not None, "If no tokenizer is provided, a stop token needs to be set manually"
             stop_tokens = [self.tokenizer.eos_token_id]
-        dec = self.batch_decoder(max_tokens, input_tokens, sample_fn)
+        dec = self.batch_decoder(max_tokens, input_tokens, sample_fn, skinny_gemm=skinny_gemm)
         if use_cuda_graph:
             dec.capture()
         outs = []

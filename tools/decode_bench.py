@@ -1,11 +1,12 @@
 """Batch-1 decode latency on one GPU: eager cached generation vs HIP-graph-captured decoding, greedy or sampled.
 
     python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64] [--sampler T,K,P | torch:T,K,P]
-                                 [--weights fp8_e4m3 [--lm-head]] [--batch B]
+                                 [--weights fp8_e4m3 [--lm-head]] [--batch B [--skinny]]
 
 ``--batch B`` times batched generation instead (``generate_batch`` / ``BatchDecoder``): B random prompts of lengths
 ``prompt, prompt - 7, prompt - 14, ...`` decoded together; ms per step, tokens/s summed over the rows, and (B <= 4:
-the graph limit) the captured loop and ``graph_tokens_equal_eager``.
+the graph limit) the captured loop and ``graph_tokens_equal_eager``.  ``--skinny`` passes ``skinny_gemm=True`` to
+``batch_decoder``: the MFMA weight-streaming kernels (``csrc/kernels/skinny.hip``) and a graph limit of 16 rows.
 
 ``--weights fp8_e4m3`` decodes the model after ``quantize_weights()`` (FP8 weight-only decoding; ``--lm-head`` includes
 the LM head); ``weights_gib`` and ``graph_gb_per_s`` then count what one decode step streams (the FP8 copies in place of
@@ -42,6 +43,7 @@ def main() -> None:
     p.add_argument("--weights", default="bf16", choices=["bf16", "fp8_e4m3"], help="fp8_e4m3: quantize_weights() first")
     p.add_argument("--lm-head", action="store_true", help="with --weights fp8_e4m3: quantise the LM head too")
     p.add_argument("--batch", type=int, default=0, help="B >= 1: time batched generation of B prompts")
+    p.add_argument("--skinny", action="store_true", help="with --batch: skinny_gemm=True (MFMA kernels, graph up to B = 16)")
     a = p.parse_args()
     from scaling_amd.models import llama_architecture
     from scaling_amd.transformer.context.config import TransformerArchitectureConfig
@@ -128,22 +130,22 @@ def main() -> None:
 
 def batch_bench(m, a, arch, sample_fn, mode, timed, quantised) -> None:
     """``--batch B``: per-step time of the batched decode loop (prefills and capture excluded)."""
-    from scaling_amd.ops.gemm import GEMV_MAX_ROWS
+    from scaling_amd.ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS
 
     B, steps = a.batch, a.tokens
     prompts = [torch.randint(1, arch.vocab_size, (max(1, a.prompt - 7 * b),)).tolist() for b in range(B)]
-    m.generate_batch(4, input_tokens=prompts, stop_tokens=[], sample_fn=sample_fn)  # warm-up
-    dec = m.batch_decoder(steps + 1, prompts, sample_fn)
+    m.generate_batch(4, input_tokens=prompts, stop_tokens=[], sample_fn=sample_fn, skinny_gemm=a.skinny)  # warm-up
+    dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny)
     te, eager = timed(lambda: dec.run([], check_every=steps + 1))
     eager_ms = 1000.0 * te / steps
     weights = sum(p.numel() * p.element_size() for p in m.parameters())
     if quantised is not None:
         weights = weights - quantised["bf16_bytes"] + quantised["fp8_bytes"]
     res = {"metric": "batched decode ms/step", "batch": B, "sampler": mode, "model": a.model, "layers": arch.num_layers,
-           "prompt": a.prompt, "tokens": steps, "weights": a.weights, "eager_ms_per_step": round(eager_ms, 3),
+           "prompt": a.prompt, "tokens": steps, "weights": a.weights, "skinny_gemm": a.skinny, "eager_ms_per_step": round(eager_ms, 3),
            "eager_tokens_per_s": round(B * 1000.0 / eager_ms, 1), "weights_gib": round(weights / 2**30, 2)}
-    if B <= GEMV_MAX_ROWS:
-        dec = m.batch_decoder(steps + 1, prompts, sample_fn)
+    if B <= (SKINNY_MAX_ROWS if a.skinny else GEMV_MAX_ROWS):
+        dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny)
         tc, _ = timed(dec.capture)
         tg, graph = timed(lambda: dec.run([], check_every=steps + 1))
         graph_ms = 1000.0 * tg / steps

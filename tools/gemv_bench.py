@@ -3,7 +3,13 @@ through the plain, epilogue-fused and norm-prologue GEMV kernels; prints us per 
 
 ``FP8=1``: the FP8-weight kernels (``csrc/kernels/gemv.hip``) of the decode step, each right after its bf16
 counterpart, in the same process, on the same shapes and under the same cold-cache protocol (``PASSES`` alternating
-passes over the list, default 2 with FP8); the rate counts the bytes each kernel streams (codes + row scales)."""
+passes over the list, default 2 with FP8); the rate counts the bytes each kernel streams (codes + row scales).
+
+``SKINNY=1``: the MFMA weight-streaming kernel (``csrc/kernels/skinny.hip``) at M = 1, 2, 3, 4, 8, 16 rows on the five 7B
+shapes in the forms the decode step runs them, each right beside its counterpart -- the GEMV at M <= 4, ``F.linear``
+(the library GEMM alone, without the norm / SwiGLU / residual the fused forms include) at M = 8 and 16 -- bf16 and
+FP8 (``SKINNY_FORMATS=bf16`` for one of them), same process, same cold-cache protocol, ``PASSES`` (default 2)
+alternating passes."""
 from __future__ import annotations
 
 import os
@@ -101,5 +107,59 @@ def main() -> None:
             print(f"{name:34s} {us:8.2f} us  {nb / us / 1e6 if nb else 0:6.2f} TB/s", flush=True)
 
 
+def skinny_main() -> None:
+    from scaling_amd.ops._ext import ext
+
+    torch.manual_seed(0)
+    dev, dt = "cuda", torch.bfloat16
+    H, F, V = 4096, 11008, 32000
+    cold = os.environ.get("COLD", "1") != "0"
+    g = torch.ones(H, device=dev, dtype=dt)
+    W = lambda ws, i: ws[i % len(ws)]  # noqa: E731
+    # (name, weight shape, K, form); forms: n0 = norm + plain, n2 = add + norm + SwiGLU, res = + residual, plain
+    layers = [("qkv norm", (3 * H, H), "n0"), ("o residual", (H, H), "res"), ("gate/up norm swiglu", (2 * F, H), "n2"),
+              ("down residual", (H, F), "res"), ("head", (V, H), "plain")]
+    print(f"skinny vs gemv / F.linear, {'cold (weights cycled through > 1 GiB)' if cold else 'warm (one weight copy)'}",
+          flush=True)
+    for fmt in os.environ.get("SKINNY_FORMATS", "bf16,fp8").split(","):
+        for name, shape, form in layers:
+            ws = copies(shape, dev, dt, cold) if fmt == "bf16" else copies8(shape, dev, cold)
+            w0 = ws[0]
+            nb = sum(t.numel() * t.element_size() for t in (w0 if isinstance(w0, tuple) else (w0,)))
+            wl = copies(shape, dev, dt, cold) if fmt == "fp8" else ws  # F.linear streams bf16 either way
+            N, K = shape
+            for p in range(int(os.environ.get("PASSES", "2"))):
+                for M in (1, 2, 3, 4, 8, 16):
+                    x = torch.randn(M, K, device=dev, dtype=dt)
+                    add = torch.randn(M, K, device=dev, dtype=dt)
+                    res = torch.randn(M, N, device=dev, dtype=dt)
+
+                    def call(kind, i, M=M, x=x, add=add, res=res):
+                        w = W(ws, i)
+                        wa = w if isinstance(w, tuple) else (w,)
+                        pre = kind + ("_w8" if fmt == "fp8" else "")
+                        if form == "n0":
+                            return getattr(ext(), pre + "_norm")(x, None, g, 1e-5, *wa, 0)
+                        if form == "n2":
+                            return getattr(ext(), pre + "_norm")(x, add, g, 1e-5, *wa, 2)
+                        if form == "res":
+                            return getattr(ext(), pre + "_residual")(x, *wa, res)
+                        return getattr(ext(), pre)(x, *wa, None)
+
+                    row = [("skinny", timeit(lambda i: call("skinny", i)))]
+                    if M <= 4:
+                        row.append(("gemv", timeit(lambda i: call("gemv", i))))
+                    else:
+                        row.append(("F.linear(bf16)", timeit(lambda i: torch.nn.functional.linear(x, W(wl, i)))))
+                    cells = "  ".join(f"{k} {us:7.2f} us {(nb if k != 'F.linear(bf16)' else N * K * 2) / us / 1e6:5.2f} TB/s"
+                                      for k, us in row)
+                    print(f"{fmt} {name:20s} pass {p} M={M:2d}  {cells}", flush=True)
+            del ws, wl
+            torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
-    main()
+    if os.environ.get("SKINNY", "0") != "0":
+        skinny_main()
+    else:
+        main()

@@ -2,7 +2,8 @@
 gemv_norm / gemv_norm_rope over bf16 and fp16 weights, and every ``gemv_w8*`` form over FP8 weights) on fixed-seed
 inputs at the tests' shapes -- M = 1..4, one wave per row and four, full / tail-only / ragged trips, bias, a
 row-strided weight view and a row-strided x: run it under two builds (``SCALING_AMD_EXT_SO``) and diff the printed
-lines to check that a kernel change is bit-identical.
+lines to check that a kernel change is bit-identical.  The same for the MFMA kernel's entry points
+(``csrc/kernels/skinny.hip``, ``skinny*`` / ``skinny_w8*``) at M = 1, 5, 16 and one shape per launch rule.
 
 usage: python tools/gemv_bits.py
 """
@@ -101,7 +102,34 @@ def run(dt, fp8: bool, rope: bool, all_paths: bool) -> None:
                       f"err {int(err.item())}", flush=True)
 
 
+def run_skinny(dt, fp8: bool) -> None:
+    tag = "w8" if fp8 else {torch.bfloat16: "bf16", torch.float16: "fp16"}[dt]
+    fn = lambda name: getattr(ext(), name.replace("skinny", "skinny_w8", 1) if fp8 else name)  # noqa: E731
+    wargs = lambda w: quant.quantize_rows_fp8(w) if fp8 else (w,)  # noqa: E731
+    # the tests' plain shapes, then one per launch rule: K split x 1 tile, K split x 2 tiles, no K split
+    for N, K in [(5, 16), (1003, 208), (64, 4112), (263, 528), (136, 528), (8200, 64), (32781, 64)]:
+        wa, w2 = wargs(weight(N + K, N, K, dt)), wargs(weight(5 + N + K, 2 * N, K, dt))
+        wv = (strided(wa[0], 64, 32),) + tuple(wa[1:])
+        gam = (1 + 0.1 * randn(3 * K, K, dt=torch.float32)).to(dt)
+        for M in (1, 5, 16):
+            x, add = randn(7 * N + K + M, M, K, dt=dt), randn(2 * (N + K) + M, M, K, dt=dt)
+            b, res = randn(3 * N + 1, N, dt=dt), randn(4 * N + M, M, N, dt=dt)
+            y = [fn("skinny")(xx, *ww, bb) for xx, ww, bb in ((x, wa, None), (x, wa, b), (x, wv, b), (strided(x, 24, 8), wa, b))]
+            print(f"{tag} skinny N={N} K={K} M={M}: y {digest(y[0])} bias {digest(y[1])} wview {digest(y[2])} "
+                  f"xview {digest(y[3])}", flush=True)
+            print(f"{tag} skinny_residual N={N} K={K} M={M}: y {digest(fn('skinny_residual')(x, *wa, res))}", flush=True)
+            print(f"{tag} skinny_swiglu F={N} K={K} M={M}: y {digest(fn('skinny_swiglu')(x, *w2))}", flush=True)
+            for a in (None, add):
+                for epi, ww in ((0, wa), (2, w2)):
+                    s, yn = fn("skinny_norm")(x, a, gam, 1e-5, *ww, epi)
+                    print(f"{tag} skinny_norm N={N} K={K} M={M} add={a is not None} epi={epi}: s {digest(s)} "
+                          f"y {digest(yn)}", flush=True)
+
+
 run(torch.bfloat16, fp8=False, rope=True, all_paths=True)
 run(torch.float16, fp8=False, rope=False, all_paths=False)  # the plain and NORM cases
 run(torch.bfloat16, fp8=True, rope=False, all_paths=True)
+run_skinny(torch.bfloat16, fp8=False)
+run_skinny(torch.float16, fp8=False)
+run_skinny(torch.bfloat16, fp8=True)
 torch.cuda.synchronize()
