@@ -167,15 +167,36 @@ at::Tensor rope(const at::Tensor& x, const at::Tensor& cosb, const at::Tensor& s
 static bool err_word(const at::Tensor& e) {
     return e.is_cuda() && e.scalar_type() == at::kInt && e.numel() >= 1;
 }
+static bool fp8_codes(const at::Tensor& t) {
+    return t.scalar_type() == at::kByte || t.scalar_type() == at::kFloat8_e4m3fn;
+}
+// FP8 K/V cache (k_scale / v_scale given): the caches hold e4m3fn codes (uint8 or float8_e4m3fn) and the scales are
+// fp32 [nkv, cache rows] (unit last stride, one common head stride).  Returns whether the operands fit the kernel.
+static bool kv_scales_ok(const char* who, const at::Tensor& qkv, const at::Tensor& kc, const at::Tensor& vc,
+                         const c10::optional<at::Tensor>& k_scale, const c10::optional<at::Tensor>& v_scale, int64_t nkv) {
+    TORCH_CHECK(k_scale.has_value() && v_scale.has_value(), who, ": k_scale and v_scale come together");
+    TORCH_CHECK(fp8_codes(kc) && fp8_codes(vc), who, ": with scales the caches must hold uint8 / float8_e4m3fn codes");
+    for (const at::Tensor* s : {&*k_scale, &*v_scale})
+        TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->dim() == 2 && s->size(0) == nkv &&
+                        s->size(1) == kc.size(0) && s->stride(1) == 1 && s->stride(0) == k_scale->stride(0),
+                    who, ": scales must be float32 GPU tensors [nkv, cache rows] with unit last stride");
+    return qkv.scalar_type() == at::kBFloat16 && qkv.size(-1) <= 512;
+}
 c10::optional<at::Tensor> rope_kv_append(const at::Tensor& qkv, const at::Tensor& cosb, const at::Tensor& sinb,
                                          const at::Tensor& pos, int64_t nq, int64_t nkv, int64_t rot_dim, bool interleaved,
-                                         at::Tensor kc, at::Tensor vc, at::Tensor err) {
+                                         at::Tensor kc, at::Tensor vc, at::Tensor err,
+                                         const c10::optional<at::Tensor>& k_scale, const c10::optional<at::Tensor>& v_scale) {
     TORCH_CHECK(err_word(err), "rope_kv_append: err must be an int32 GPU tensor");
     check_cuda(qkv, "qkv");
     const int64_t hd = qkv.size(-1);
+    const bool q8 = k_scale.has_value() || v_scale.has_value();
+    TORCH_CHECK(!q8 || (kc.dim() == 3 && vc.dim() == 3 && kc.is_cuda() && vc.is_cuda()),
+                "rope_kv_append: caches must be [rows, nkv, hd] GPU tensors");
+    if (q8 && !kv_scales_ok("rope_kv_append", qkv, kc, vc, k_scale, v_scale, nkv)) return c10::nullopt;
+    const auto cdt = q8 ? kc.scalar_type() : qkv.scalar_type();
     if (!(qkv.is_contiguous() && qkv.numel() == (nq + 2 * nkv) * hd && kc.is_contiguous() && vc.is_contiguous() &&
           kc.dim() == 3 && kc.size(1) == nkv && kc.size(2) == hd && vc.sizes() == kc.sizes() &&
-          kc.scalar_type() == qkv.scalar_type() && vc.scalar_type() == qkv.scalar_type() && pos.is_cuda() &&
+          kc.scalar_type() == cdt && vc.scalar_type() == cdt && pos.is_cuda() &&
           pos.scalar_type() == at::kLong && pos.numel() == 1 && cosb.scalar_type() == at::kFloat &&
           cosb.is_contiguous() && sinb.is_contiguous() && cosb.size(-1) == rot_dim / 2 &&
           (uintptr_t)qkv.data_ptr() % 16 == 0 && (uintptr_t)kc.data_ptr() % 16 == 0 && (uintptr_t)vc.data_ptr() % 16 == 0))
@@ -185,7 +206,8 @@ c10::optional<at::Tensor> rope_kv_append(const at::Tensor& qkv, const at::Tensor
     if (!sa_launch::rope_kv_append(dt(qkv), interleaved, qkv.data_ptr(), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
                                    pos.data_ptr<int64_t>(), cosb.data_ptr<float>(), sinb.data_ptr<float>(), (int)nq,
                                    (int)nkv, (int)hd, (int)rot_dim, std::min<int64_t>(kc.size(0), cosb.size(0)),
-                                   err.data_ptr<int>(), cur_stream()))
+                                   err.data_ptr<int>(), cur_stream(), 1, 0, q8 ? k_scale->data_ptr<float>() : nullptr,
+                                   q8 ? v_scale->data_ptr<float>() : nullptr, q8 ? k_scale->stride(0) : 0))
         return c10::nullopt;
     return q;
 }
@@ -194,16 +216,21 @@ c10::optional<at::Tensor> rope_kv_append(const at::Tensor& qkv, const at::Tensor
 // [B, nq, hd].  Row b equals rope_kv_append on that sequence's slab bit for bit (the same kernel, blockIdx.y = b).
 c10::optional<at::Tensor> rope_kv_append_batch(const at::Tensor& qkv, const at::Tensor& cosb, const at::Tensor& sinb,
                                                const at::Tensor& pos, int64_t nq, int64_t nkv, int64_t rot_dim,
-                                               bool interleaved, at::Tensor kc, at::Tensor vc, at::Tensor err, int64_t cap) {
+                                               bool interleaved, at::Tensor kc, at::Tensor vc, at::Tensor err, int64_t cap,
+                                               const c10::optional<at::Tensor>& k_scale,
+                                               const c10::optional<at::Tensor>& v_scale) {
     TORCH_CHECK(err_word(err), "rope_kv_append_batch: err must be an int32 GPU tensor");
     check_cuda(qkv, "qkv");
     TORCH_CHECK(qkv.dim() == 3 && cap > 0, "rope_kv_append_batch: qkv must be [B, nq + 2 nkv, hd] and cap positive");
     const int64_t B = qkv.size(0), hd = qkv.size(-1);
     TORCH_CHECK(kc.dim() == 3 && kc.size(0) == B * cap && vc.sizes() == kc.sizes() && pos.numel() == B,
                 "rope_kv_append_batch: caches must hold B * cap rows and pos one entry per sequence");
+    const bool q8 = k_scale.has_value() || v_scale.has_value();
+    if (q8 && !kv_scales_ok("rope_kv_append_batch", qkv, kc, vc, k_scale, v_scale, nkv)) return c10::nullopt;
+    const auto cdt = q8 ? kc.scalar_type() : qkv.scalar_type();
     if (!(B >= 1 && qkv.is_contiguous() && qkv.size(1) == nq + 2 * nkv && kc.is_contiguous() && vc.is_contiguous() &&
-          kc.size(1) == nkv && kc.size(2) == hd && kc.scalar_type() == qkv.scalar_type() &&
-          vc.scalar_type() == qkv.scalar_type() && kc.is_cuda() && vc.is_cuda() && pos.is_cuda() &&
+          kc.size(1) == nkv && kc.size(2) == hd && kc.scalar_type() == cdt &&
+          vc.scalar_type() == cdt && kc.is_cuda() && vc.is_cuda() && pos.is_cuda() &&
           pos.scalar_type() == at::kLong && pos.is_contiguous() && cosb.is_cuda() && sinb.is_cuda() &&
           cosb.scalar_type() == at::kFloat && sinb.scalar_type() == at::kFloat && cosb.is_contiguous() &&
           sinb.is_contiguous() && cosb.size(-1) == rot_dim / 2 && sinb.sizes() == cosb.sizes() && rot_dim <= hd &&
@@ -214,7 +241,8 @@ c10::optional<at::Tensor> rope_kv_append_batch(const at::Tensor& qkv, const at::
     if (!sa_launch::rope_kv_append(dt(qkv), interleaved, qkv.data_ptr(), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
                                    pos.data_ptr<int64_t>(), cosb.data_ptr<float>(), sinb.data_ptr<float>(), (int)nq,
                                    (int)nkv, (int)hd, (int)rot_dim, std::min<int64_t>(cap, cosb.size(0)),
-                                   err.data_ptr<int>(), cur_stream(), (int)B, cap))
+                                   err.data_ptr<int>(), cur_stream(), (int)B, cap, q8 ? k_scale->data_ptr<float>() : nullptr,
+                                   q8 ? v_scale->data_ptr<float>() : nullptr, q8 ? k_scale->stride(0) : 0))
         return c10::nullopt;
     return q;
 }
@@ -626,11 +654,32 @@ uint32_t drop_threshold(double p) {
 std::vector<at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& cu_q,
                                const at::Tensor& cu_k, int64_t max_q, double scale, bool causal, int64_t window,
                                double p_drop, int64_t seed, int64_t local_heads, int64_t max_k,
-                               const c10::optional<at::Tensor>& k_range) {
+                               const c10::optional<at::Tensor>& k_range, const c10::optional<at::Tensor>& k_scale,
+                               const c10::optional<at::Tensor>& v_scale) {
     // k_range: int32 [nseg, 2] = (first key row, key count) per segment, replacing cu_k (decode kernel only): the
     // keys of a static batched cache sit in one fixed-capacity slab per sequence, not packed back to back
-    check_qkv(q, "q"); check_qkv(k, "k"); check_qkv(v, "v");
-    TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type(), "flash_attn: q/k/v dtypes differ");
+    // k_scale / v_scale: FP8 K/V (decode kernel only, bf16 q): k / v hold e4m3fn codes (uint8 or float8_e4m3fn) and the
+    // scales are fp32 [Hkv, key rows], one power of two per (kv head, row)
+    const bool q8 = k_scale.has_value() || v_scale.has_value();
+    check_qkv(q, "q");
+    if (q8) {
+        TORCH_CHECK(k_scale.has_value() && v_scale.has_value(), "flash_attn: k_scale and v_scale come together");
+        for (const at::Tensor* t : {&k, &v}) {
+            TORCH_CHECK(t->is_cuda() && t->dim() == 3 && t->stride(2) == 1, "flash_attn: FP8 k / v must be [T, heads, D] with unit last stride");
+            TORCH_CHECK(fp8_codes(*t), "flash_attn: with k_scale / v_scale, k and v must be uint8 or float8_e4m3fn codes");
+            TORCH_CHECK(t->stride(0) % 16 == 0 && t->stride(1) % 16 == 0 && (uintptr_t)t->data_ptr() % 16 == 0,
+                        "flash_attn: FP8 k / v strides and addresses must be multiples of 16 bytes");
+        }
+        TORCH_CHECK(q.scalar_type() == at::kBFloat16, "flash_attn: FP8 k / v need bfloat16 queries (an e4m3 code times its scale is exact in bfloat16, not in float16)");
+        TORCH_CHECK(v.size(0) == k.size(0), "flash_attn: k and v must hold the same number of rows");
+        for (const at::Tensor* s : {&*k_scale, &*v_scale})
+            TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->dim() == 2 && s->size(0) == k.size(1) &&
+                            s->size(1) == k.size(0) && s->stride(1) == 1 && s->stride(0) == k_scale->stride(0),
+                        "flash_attn: k_scale / v_scale must be float32 GPU tensors [kv heads, key rows] with unit last stride");
+    } else {
+        check_qkv(k, "k"); check_qkv(v, "v");
+        TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type(), "flash_attn: q/k/v dtypes differ");
+    }
     TORCH_CHECK(p_drop >= 0.0 && p_drop < 1.0, "flash_attn: dropout probability must be in [0, 1)");
     const int64_t D = q.size(2);
     TORCH_CHECK(D == 32 || D == 64 || D == 128, "flash_attn: head dim must be 32, 64 or 128");
@@ -660,12 +709,17 @@ std::vector<at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const a
                     "no dropout)");
         TORCH_CHECK(v.size(0) == k.size(0), "flash_attn: k and v must hold the same number of rows");
     }
+    if (q8)
+        TORCH_CHECK(p_drop == 0.0 && max_q * grp <= 32,
+                    "flash_attn: FP8 k / v are supported by the decode kernel only (max_q * heads per kv head <= 32, "
+                    "no dropout)");
     if (T > 0 && a.nseg > 0 && p_drop == 0.0 && max_q * grp <= 32) {
         // short query segments (decode): GQA-packed rows, split-K over the keys, then a combine pass
         DecArgs d{};
         d.q = a.q; d.k = a.k; d.v = a.v;
         d.q_tok = a.q_tok; d.q_head = a.q_head; d.k_tok = a.k_tok; d.k_head = a.k_head; d.v_tok = a.v_tok; d.v_head = a.v_head;
         d.cu_q = a.cu_q; d.cu_k = a.cu_k; d.nseg = a.nseg;
+        if (q8) { d.k_scale = k_scale->data_ptr<float>(); d.v_scale = v_scale->data_ptr<float>(); d.s_head = k_scale->stride(0); }
         d.k_range = k_range.has_value() ? k_range->data_ptr<int>() : nullptr; d.k_rows = k.size(0); d.Hq = a.Hq; d.Hkv = a.Hkv; d.causal = a.causal;
         d.window = a.window; d.local_heads = a.local_heads; d.scale_log2 = a.scale_log2; d.Tq = T;
         sa_launch::fa_decode_plan(max_k > 0 ? max_k : k.size(0), a.Hkv, a.nseg, d.split_keys, d.nsplit);
@@ -968,8 +1022,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemm_tn_ok", &gemm_tn_ok, "whether gemm_tn supports these operands");
     m.def("gemm_tn", &gemm_tn, "C (+)= A^T B for k-major bf16 operands (weight-gradient GEMM)");
     m.def("rope", &rope, "rotary embedding (fwd / inverse), optional strided / in-place output", py::arg("x"), py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("rot_dim"), py::arg("seq_len"), py::arg("interleaved"), py::arg("inverse"), py::arg("out") = py::none());
-    m.def("rope_kv_append", &rope_kv_append, "graph decode: RoPE q, RoPE k into the K cache row, v into the V cache row");
-    m.def("rope_kv_append_batch", &rope_kv_append_batch, "batched graph decode: rope_kv_append for one token of each of B sequences, one launch");
+    m.def("rope_kv_append", &rope_kv_append, "graph decode: RoPE q, RoPE k into the K cache row, v into the V cache row (k_scale / v_scale: FP8 e4m3 cache)",
+          py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("nq"), py::arg("nkv"), py::arg("rot_dim"), py::arg("interleaved"),
+          py::arg("kc"), py::arg("vc"), py::arg("err"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+    m.def("rope_kv_append_batch", &rope_kv_append_batch, "batched graph decode: rope_kv_append for one token of each of B sequences, one launch",
+          py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("nq"), py::arg("nkv"), py::arg("rot_dim"), py::arg("interleaved"),
+          py::arg("kc"), py::arg("vc"), py::arg("err"), py::arg("cap"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
     m.def("xent_stats", &xent_stats, "cross-entropy row statistics");
     m.def("xent_bwd", &xent_bwd, "cross-entropy backward");
     m.def("embed_fwd", &embed_fwd, "vocab-parallel embedding forward");
@@ -991,6 +1049,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("xgmi_emulate", &xgmi_emulate, "per-rank proxy: emulated collective (HBM traffic on nwg CUs, held to us)",
           py::arg("src"), py::arg("scratch"), py::arg("bytes"), py::arg("us"), py::arg("nwg") = 16);
     m.def("dropout_add", &dropout_add, "residual + dropout(x) with a hashed keep mask", py::arg("x"), py::arg("res"), py::arg("p"), py::arg("seed"));
-    m.def("fa_fwd", &fa_fwd, "flash attention forward (bf16/fp16, optional attention dropout)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("max_k") = -1, py::arg("k_range") = py::none());
+    m.def("fa_fwd", &fa_fwd, "flash attention forward (bf16/fp16, optional attention dropout)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("max_k") = -1, py::arg("k_range") = py::none(), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
     m.def("fa_bwd", &fa_bwd, "flash attention backward (optional strided dq/dk/dv outputs)", py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("max_k"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(), py::arg("dv_out") = py::none(), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("rope_cos") = py::none(), py::arg("rope_sin") = py::none(), py::arg("rope_pos") = py::none(), py::arg("rope_dim") = 0, py::arg("rope_seq") = 1, py::arg("rope_interleaved") = false);
 }

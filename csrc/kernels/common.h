@@ -27,6 +27,16 @@ __device__ __forceinline__ u16 f2bf(float f) {
 }
 __device__ __forceinline__ float round_bf(float f) { return bf2f(f2bf(f)); }
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+// four OCP e4m3 codes (one dword, memory order) -> four bf16 in two dwords: v_cvt_pk_f32_fp8, keeping the high half of
+// each exact fp32 value (e4m3 has 3 mantissa bits and its subnormals are normal bf16 numbers, so nothing is dropped)
+__device__ __forceinline__ void e4m3x4_to_bf16(uint32_t r, uint32_t& o0, uint32_t& o1) {
+    const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)r, false);
+    const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)r, true);
+    o0 = (__float_as_uint(lo[0]) >> 16) | (__float_as_uint(lo[1]) & 0xffff0000u);
+    o1 = (__float_as_uint(hi[0]) >> 16) | (__float_as_uint(hi[1]) & 0xffff0000u);
+}
+
 template <typename T> struct IO;
 template <> struct IO<float> {
     __device__ static __forceinline__ float ld(const float* p, int64_t i) { return p[i]; }

@@ -15,6 +15,18 @@
 // the prefill kernels.  Rows / keys past their ranges contribute nothing.
 // A segment's keys are rows [cu_k[seg], cu_k[seg + 1]) or, with DecArgs::k_range, rows [start, start + length) of a
 // buffer that holds one fixed-capacity slab per sequence (batched decoding over a static cache).
+//
+// FP8 K/V (template flag Q8, bf16 queries; DecArgs::k_scale): K and V are OCP e4m3fn codes with one fp32 power-of-two
+// scale per (kv head, row) -- an exact encoding of a bf16 cache (ops/quant.py).  Same tiles, split plan, dim-to-MFMA
+// mapping, masking and partials as the bf16 form; per tile a lane loads
+//  * 8 K codes per MFMA step (8 bytes where the bf16 form loads 16), decoded to bf16 in registers (e4m3x4_to_bf16) for
+//    the same MFMA; the key's scale multiplies its fp32 score before the softmax scale, x = (s ks[key]) c2 -- a power of
+//    two on an fp32 accumulator is exact, so x is the bf16 kernel's score on the dequantised cache;
+//  * 16 V codes per pass, decoded, multiplied by the row's scale (a bf16 number, exactly) and written into the same
+//    swizzled LDS image, so the transposed reads and the P V MFMAs are untouched.  (Folding the V scale into P instead
+//    would be equal only short of underflow of P; the image form has no such condition and was kept.)
+// o and lse are bit for bit those of the bf16 kernel on the dequantised cache.  Rows past k_end load neither codes nor
+// scales.
 #include <algorithm>
 
 #include "flash_attn.h"
@@ -24,6 +36,10 @@ using namespace sa;
 using namespace sa::fa;
 
 namespace {
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // four floats at a dword-aligned address
 
 // out[token][hq][d] = sum_s 2^(m_s - M) O_s[d] / sum_s 2^(m_s - M) l_s ; lse = (M + log2 L) ln 2 (written for d == 0)
 template <int D, bool F16>
@@ -68,8 +84,9 @@ __device__ __forceinline__ void merge_dim(const DecArgs& a, int64_t tok, int hq,
     if (d == 0) a.lse[(int64_t)hq * a.lse_stride + tok] = L > 0.f ? (M + __log2f(L)) * 0.69314718055994530942f : INFINITY;
 }
 
-template <int D, bool F16>
+template <int D, bool F16, bool Q8>
 __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
+    static_assert(!(F16 && Q8), "FP8 K/V: bf16 queries only");
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ __attribute__((aligned(16))) char vimg[32 * D * 2];
     constexpr int NKS = D / 16, NT = D / 32;
@@ -113,33 +130,123 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
     float m = -INFINITY, l = 0.f;
     const u16* kb = a.k + (int64_t)k0s * a.k_tok + (int64_t)hk * a.k_head;
     const u16* vb = a.v + (int64_t)k0s * a.v_tok + (int64_t)hk * a.v_head;
+    // FP8 K/V: codes, one byte per element (strides in bytes), and the per-row scales of this kv head
+    const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(a.k) + (int64_t)k0s * a.k_tok + (int64_t)hk * a.k_head;
+    const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(a.v) + (int64_t)k0s * a.v_tok + (int64_t)hk * a.v_head;
+    const float* ksb = Q8 ? a.k_scale + (int64_t)hk * a.s_head + k0s : nullptr;
+    const float* vsb = Q8 ? a.v_scale + (int64_t)hk * a.s_head + k0s : nullptr;
+
+    // FP8: the codes and scales of a tile are loaded two tiles ahead (n1, n2).  A tile of codes is half the bytes of a
+    // bf16 tile and a workgroup is one wave, so two tiles in flight are the bf16 form's bytes in flight, and their round
+    // trip overlaps the decode -> MFMA -> softmax -> MFMA chain of the tile being computed.  The loads are unconditional
+    // instructions (every lane guards its own rows against k_end), so the waits stay counted, not drained.
+    // QP 16-byte V loads per lane: 16 codes = two 8-element chunks of the image
+    constexpr int QP = 32 * D / 16 / 64;
+    struct Q8Tile {
+        u32x2 kq[NKS];  // K codes: key kt + r, dims 16 ks + 8 h ..
+        f32x4 ksc[4];   // K scales of the keys of this lane's 16 score registers: group g = keys kt + 8 g + 4 h + 0..3
+        u32x4 vq[QP];
+        float vs[QP];
+    };
+    auto load_q8 = [&](int kt, Q8Tile& t) {  // rows past k_end load neither codes nor scales
+        const bool krow = kt + r < k_end;
+        const uint8_t* kp = kb8 + (int64_t)(krow ? kt + r : kt) * a.k_tok;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks)
+            t.kq[ks] = krow ? *reinterpret_cast<const u32x2*>(kp + 16 * ks + 8 * h) : u32x2{0, 0};
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int kg = kt + 8 * g + 4 * h;
+            if (kg + 3 < k_end) {  // one 16-byte load; a slab may start at any row, so only dword alignment is assumed
+                t.ksc[g] = *reinterpret_cast<const f32x4_a4*>(ksb + kg);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) t.ksc[g][i] = kg + i < k_end ? ksb[kg + i] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < QP; ++p) {
+            const int id = lane + 64 * p, row = id / (D / 16), c = id % (D / 16);
+            const bool on = kt + row < k_end;
+            t.vq[p] = on ? *reinterpret_cast<const u32x4*>(vb8 + (int64_t)(kt + row) * a.v_tok + c * 16) : u32x4{0, 0, 0, 0};
+            t.vs[p] = on ? vsb[kt + row] : 0.f;
+        }
+    };
+    Q8Tile n1, n2;
+    if constexpr (Q8) {
+        load_q8(k_begin, n1);
+        load_q8(k_begin + 32, n2);
+    }
 
     for (int kt = k_begin; kt < k_end; kt += 32) {
         // K rows (A operand: key kt + r, dims 16 ks + 8 h) and the V tile are all issued before anything waits on
         // them: one memory round trip per tile instead of V, then K
         const bool krow = kt + r < k_end;
-        const u16* kp = kb + (int64_t)(krow ? kt + r : kt) * a.k_tok;
         u16x8 kv[NKS];
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks)
-            kv[ks] = krow ? *reinterpret_cast<const u16x8*>(kp + 16 * ks + 8 * h) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        // V tile [32][D] -> swizzled LDS image (rows past k_end as zeros)
-        constexpr int PASSES = 32 * D / 8 / 64;
+        // PASSES 16-byte loads per lane of 8 bf16 each
+        constexpr int PASSES = Q8 ? 1 : 32 * D / 8 / 64;
         u16x8 vv[PASSES];
+        Q8Tile cur;
+        if constexpr (Q8) {
+            cur = n1;
+            n1 = n2;
+            load_q8(kt + 64, n2);
+            // codes -> bf16 in registers (exact); the key's scale multiplies its fp32 score below
 #pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            const int id = lane + 64 * p, row = id / (D / 8), c = id % (D / 8);
-            vv[p] = kt + row < k_end ? *reinterpret_cast<const u16x8*>(vb + (int64_t)(kt + row) * a.v_tok + c * 8)
-                                     : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            for (int ks = 0; ks < NKS; ++ks) {
+                u32x4 w;
+                uint32_t w0, w1;
+                e4m3x4_to_bf16(cur.kq[ks][0], w0, w1);
+                w[0] = w0;
+                w[1] = w1;
+                e4m3x4_to_bf16(cur.kq[ks][1], w0, w1);
+                w[2] = w0;
+                w[3] = w1;
+                kv[ks] = __builtin_bit_cast(u16x8, w);
+            }
+        } else {
+            const u16* kp = kb + (int64_t)(krow ? kt + r : kt) * a.k_tok;
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks)
+                kv[ks] = krow ? *reinterpret_cast<const u16x8*>(kp + 16 * ks + 8 * h) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            // V tile [32][D] -> swizzled LDS image (rows past k_end as zeros)
+#pragma unroll
+            for (int p = 0; p < PASSES; ++p) {
+                const int id = lane + 64 * p, row = id / (D / 8), c = id % (D / 8);
+                vv[p] = kt + row < k_end ? *reinterpret_cast<const u16x8*>(vb + (int64_t)(kt + row) * a.v_tok + c * 8)
+                                         : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            }
         }
         // S^T = K Q^T
         f32x16 s = f32x16{};
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) s = mma<F16>(__builtin_bit_cast(bf16x8, kv[ks]), qf[ks], s);
+        if constexpr (Q8) {
+            // V codes times the row's scale are bf16 numbers (exact: the product has 4 significant bits and the scale
+            // exponent is bounded below), written into the image the bf16 kernel would have loaded
 #pragma unroll
-        for (int p = 0; p < PASSES; ++p) {
-            const int id = lane + 64 * p, row = id / (D / 8), c = id % (D / 8);
-            *reinterpret_cast<u16x8*>(vimg + row * D * 2 + 16 * swz<D>(row, c)) = vv[p];
+            for (int p = 0; p < QP; ++p) {
+                const int id = lane + 64 * p, row = id / (D / 16), c = id % (D / 16);
+                const float vsp = cur.vs[p];
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    u32x4 w;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)cur.vq[p][2 * q + i], false);
+                        const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)cur.vq[p][2 * q + i], true);
+                        w[2 * i] = (__float_as_uint(lo[0] * vsp) >> 16) | (__float_as_uint(lo[1] * vsp) & 0xffff0000u);
+                        w[2 * i + 1] = (__float_as_uint(hi[0] * vsp) >> 16) | (__float_as_uint(hi[1] * vsp) & 0xffff0000u);
+                    }
+                    *reinterpret_cast<u32x4*>(vimg + row * D * 2 + 16 * swz<D>(row, 2 * c + q)) = w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int p = 0; p < PASSES; ++p) {
+                const int id = lane + 64 * p, row = id / (D / 8), c = id % (D / 8);
+                *reinterpret_cast<u16x8*>(vimg + row * D * 2 + 16 * swz<D>(row, c)) = vv[p];
+            }
         }
         // scale + mask; key of register j: kt + crow(j) + 4h
         float mx = -INFINITY;
@@ -149,7 +256,9 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
             bool ok = valid && key < k_end;
             if (a.causal) ok = ok && key <= qi + off;
             if (win >= 0) ok = ok && key >= qi + off - win && (a.causal || key <= qi + off + win);
-            const float x = ok ? s[j] * c2 : -INFINITY;
+            float x;
+            if constexpr (Q8) x = ok ? (s[j] * cur.ksc[j >> 2][j & 3]) * c2 : -INFINITY;  // power-of-two scale: exact, before c2
+            else x = ok ? s[j] * c2 : -INFINITY;
             s[j] = x;
             mx = fmaxf(mx, x);
         }
@@ -201,7 +310,13 @@ __global__ __launch_bounds__(D) void fa_decode_combine_kernel(DecArgs a) {
 
 template <int D, bool F16>
 void launch(const DecArgs& a, int nseg, hipStream_t st) {
-    hipLaunchKernelGGL((fa_decode_kernel<D, F16>), dim3(a.nsplit, a.Hkv, nseg), dim3(64), 0, st, a);
+    const dim3 grid(a.nsplit, a.Hkv, nseg);
+    bool q8 = false;
+    if constexpr (!F16) {
+        q8 = a.k_scale != nullptr;
+        if (q8) hipLaunchKernelGGL((fa_decode_kernel<D, false, true>), grid, dim3(64), 0, st, a);
+    }
+    if (!q8) hipLaunchKernelGGL((fa_decode_kernel<D, F16, false>), grid, dim3(64), 0, st, a);
     hipLaunchKernelGGL((fa_decode_combine_kernel<D, F16>), dim3((unsigned)a.Tq, a.Hq), dim3(D), 0, st, a);
 }
 

@@ -45,7 +45,6 @@ namespace {
 enum { EPI_NONE = 0, EPI_RES = 1, EPI_SWIGLU = 2, EPI_ROPE = 3 };
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Weight formats: T the element type of W's pointer arithmetic (ldw counts T's), P = 1 << kLog2P weights per 16-byte
 // piece, S one piece as it is held across a trip (ld) until piece() turns it into P floats (unpack).

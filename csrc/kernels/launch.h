@@ -29,9 +29,15 @@ void rope(int dtype, bool interleaved, const void* x, int64_t x_tok, int64_t x_h
 // lim = min(cache rows, rotary table rows); a position outside [0, lim) writes nothing but zeros into q and sets *err
 // B > 1: one token of each of B sequences (x [B][nq + 2 nkv][hd], pos [B], q_out [B][nq][hd]); sequence b owns cache
 // rows [b * cap, (b + 1) * cap) and writes row b * cap + pos[b]; lim = min(cap, rotary table rows), per sequence
+// k_scale != nullptr (bf16 x only): the FP8 K/V cache.  kc / vc hold OCP e4m3fn codes, one byte per element, and
+// k_scale / v_scale [nkv][s_head] one fp32 power-of-two scale per (kv head, cache row): the rotated, bf16-rounded k
+// row and the v row are quantised per row exactly as ops/quant.py quantize_rows_fp8 does.  q_out is bitwise the bf16
+// form's.  A k / v value that is NaN is stored as 0, one above 2^127 (infinity included) as +-2^127; bit 1 of *err is
+// then set (bit 0: the position error)
 bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, void* kc, void* vc, const int64_t* pos,
                     const float* cosb, const float* sinb, int nq, int nkv, int hd, int rd, int64_t lim, int* err,
-                    hipStream_t st, int B = 1, int64_t cap = 0);
+                    hipStream_t st, int B = 1, int64_t cap = 0, float* k_scale = nullptr, float* v_scale = nullptr,
+                    int64_t s_head = 0);
 }  // namespace sa_launch
 
 namespace sa_launch {
@@ -86,6 +92,10 @@ struct DecArgs {
     // optional [nseg][2] = (first key row, key count) per segment: replaces cu_k for keys that are not packed back
     // to back (one fixed-capacity slab per sequence); k_rows = rows of the key buffer, ranges are clipped to it
     const int* k_range; int64_t k_rows;
+    // FP8 K/V (k_scale != nullptr, bf16 q only): k / v point at OCP e4m3fn codes, one byte per element with the
+    // strides above counted in bytes; row t of kv head h carries the fp32 power-of-two scales k_scale[h * s_head + t]
+    // and v_scale[h * s_head + t] (t a row of the key buffer, as in cu_k / k_range)
+    const float* k_scale; const float* v_scale; int64_t s_head;
     int nseg, Hq, Hkv, causal, window, local_heads;
     float scale_log2;
     int split_keys, nsplit;

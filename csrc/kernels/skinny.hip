@@ -52,7 +52,6 @@ namespace {
 enum { EPI_NONE = 0, EPI_RES = 1, EPI_SWIGLU = 2 };
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -106,20 +105,14 @@ struct E4M3W {
     typedef uint8_t T;
     static constexpr int P = 16, H = 2;
     static constexpr bool kScaled = true;
-    // four codes -> four bf16 (the high halves of their exact fp32 values), in memory order
-    __device__ static __forceinline__ void word(uint32_t r, uint32_t& o0, uint32_t& o1) {
-        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)r, false);
-        const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)r, true);
-        o0 = (__float_as_uint(lo[0]) >> 16) | (__float_as_uint(lo[1]) & 0xffff0000u);
-        o1 = (__float_as_uint(hi[0]) >> 16) | (__float_as_uint(hi[1]) & 0xffff0000u);
-    }
+    // eight codes -> eight bf16 in memory order (e4m3x4_to_bf16, common.h)
     __device__ static __forceinline__ u32x4 frag(const u32x4& w, int hh) {
         u32x4 r;
         uint32_t a, b;
-        word(w[2 * hh], a, b);
+        e4m3x4_to_bf16(w[2 * hh], a, b);
         r[0] = a;
         r[1] = b;
-        word(w[2 * hh + 1], a, b);
+        e4m3x4_to_bf16(w[2 * hh + 1], a, b);
         r[2] = a;
         r[3] = b;
         return r;

@@ -163,6 +163,45 @@ __global__ __launch_bounds__(256) void rope_kernel(const T* __restrict__ x, T* _
 // lim = min(cap, rotary table rows): a sequence whose position is outside [0, lim) writes no cache row, zeros its own
 // q row and sets *err (the caller checks the word on the host; an out-of-range row index would otherwise write past
 // its slab silently); the other sequences are unaffected.
+// Chunk c of one row of the append step (CR = rc + (hd - rd) / 8 chunks, rc of them rotating, as rope_v8_kernel): the
+// values before rounding, a[8] for elements ea.. and -- NeoX rotating chunks -- b[8] for elements eb.. (eb < 0: none).
+// Shared by the bf16 and the FP8 append kernels, so both round the same numbers.
+template <typename T, bool IL>
+__device__ __forceinline__ void append_chunk(const T* xr, int c, int rc, int half, int rd, const float* cb,
+                                             const float* sb, float (&a)[8], float (&b)[8], int& ea, int& eb) {
+    eb = -1;
+    if (c < rc) {
+        if (!IL) {
+            const int p = c * 8;
+            float x0[8], x1[8], cs[8], sn[8];
+            V8<T>::ld(xr + p, x0);
+            V8<T>::ld(xr + half + p, x1);
+            V8<float>::ld(cb + p, cs);
+            V8<float>::ld(sb + p, sn);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                rot_pair(x0[j], x1[j], cs[j], sn[j], a[j], b[j]);
+            }
+            ea = p;
+            eb = half + p;
+        } else {
+            const int e = c * 8;
+            float v[8];
+            V8<T>::ld(xr + e, v);
+            const f32x4 cs = *reinterpret_cast<const f32x4*>(cb + e / 2);
+            const f32x4 sn = *reinterpret_cast<const f32x4*>(sb + e / 2);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                rot_pair(v[2 * j], v[2 * j + 1], cs[j], sn[j], a[2 * j], a[2 * j + 1]);
+            }
+            ea = e;
+        }
+    } else {
+        ea = rd + (c - rc) * 8;
+        V8<T>::ld(xr + ea, a);
+    }
+}
+
 template <typename T, bool IL>
 __global__ __launch_bounds__(256) void rope_kv_append_kernel(const T* __restrict__ x, T* __restrict__ q_out,
                                                              T* __restrict__ kc, T* __restrict__ vc,
@@ -201,41 +240,121 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(const T* __restrict
             }
             continue;
         }
-        if (c < rc) {
-            const float* cb = cosb + ps * half;
-            const float* sb = sinb + ps * half;
-            if (!IL) {
-                const int p = c * 8;
-                float x0[8], x1[8], cs[8], sn[8], o0[8], o1[8];
-                V8<T>::ld(xr + p, x0);
-                V8<T>::ld(xr + half + p, x1);
-                V8<float>::ld(cb + p, cs);
-                V8<float>::ld(sb + p, sn);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    rot_pair(x0[j], x1[j], cs[j], sn[j], o0[j], o1[j]);
-                }
-                V8<T>::st(orow + p, o0);
-                V8<T>::st(orow + half + p, o1);
-            } else {
-                const int e = c * 8;
-                float v[8], o[8];
-                V8<T>::ld(xr + e, v);
-                const f32x4 cs = *reinterpret_cast<const f32x4*>(cb + e / 2);
-                const f32x4 sn = *reinterpret_cast<const f32x4*>(sb + e / 2);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    rot_pair(v[2 * j], v[2 * j + 1], cs[j], sn[j], o[2 * j], o[2 * j + 1]);
-                }
-                V8<T>::st(orow + e, o);
-            }
-        } else {
-            const int e = rd + (c - rc) * 8;
-            float v[8];
-            V8<T>::ld(xr + e, v);
-            V8<T>::st(orow + e, v);
-        }
+        float o0[8], o1[8];
+        int e0, e1;
+        append_chunk<T, IL>(xr, c, rc, half, rd, cosb + ps * half, sinb + ps * half, o0, o1, e0, e1);
+        V8<T>::st(orow + e0, o0);
+        if (e1 >= 0) V8<T>::st(orow + e1, o1);
     }
+}
+
+// a k / v value as the bf16 cache would hold it; NaN becomes 0 and a magnitude above 2^127 (infinity included) +-2^127:
+// a row whose amax lies in (240 * 2^120, bf16 max] would round it to the code of 256 at scale 2^120, and 256 * 2^120 is
+// 2^128, infinite in bf16.  The cut sits at the power of two below, 2^127, where amax / s <= 448 * 2^119 stays finite
+// (ops/quant.py sanitize_kv is the torch form)
+__device__ __forceinline__ float kv_finite_bf(float v, bool& bad) {
+    uint32_t u = f2bf(v);
+    if ((u & 0x7fffu) > 0x7f00u) {
+        bad = true;
+        u = (u & 0x7fffu) > 0x7f80u ? 0u : ((u & 0x8000u) | 0x7f00u);
+    }
+    return bf2f((u16)u);
+}
+// eight values times inv -> eight e4m3fn codes (v_cvt_pk_fp8_f32: round to nearest even), in memory order
+__device__ __forceinline__ uint2 e4m3_pack8(const float (&v)[8], float inv) {
+    int w0 = 0, w1 = 0;
+    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, w0, false);
+    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, w0, true);
+    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, w1, false);
+    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, w1, true);
+    return make_uint2((uint32_t)w0, (uint32_t)w1);
+}
+
+// rope_kv_append_kernel over an FP8 K/V cache (bf16 x): kc / vc hold e4m3fn codes [B * cap][nkv][hd], one byte each, and
+// k_scale / v_scale [nkv][s_head] one fp32 power-of-two scale per (kv head, cache row).  Waves [0, 2 nkv) of a sequence
+// take one k or v head each, so the row's amax is one 64-lane reduction: lane c holds chunk c of the row (append_chunk:
+// the numbers the bf16 kernel rounds), rounds it to bf16 -- the value the bf16 cache would hold --, and the row is
+// quantised as ops/quant.py quantize_rows_fp8 does: s = 2^e the smallest power of two with amax <= 448 s, e >= -100,
+// s = 1 for an all-zero row, formed from amax's exponent and mantissa bits (amax / 448 = m 2^e with m <= 1/2 exactly
+// when amax's significand is <= 1.75); codes = e4m3(value / s), |value / s| <= 448 by construction.  The remaining
+// waves rotate the q heads, one lane per chunk as the bf16 kernel (q_out is bitwise its output).  A non-finite k / v
+// value never becomes the NaN code: kv_finite_bf replaces it and bit 1 of *err is set; bit 0 is the position error.
+template <bool IL>
+__global__ __launch_bounds__(256) void rope_kv_append_q8_kernel(const u16* __restrict__ x, u16* __restrict__ q_out,
+                                                                uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
+                                                                float* __restrict__ k_scale, float* __restrict__ v_scale,
+                                                                int64_t s_head, const int64_t* __restrict__ pos,
+                                                                const float* cosb, const float* sinb, int nq, int nkv,
+                                                                int hd, int rd, int64_t lim, int64_t cap,
+                                                                int* __restrict__ err) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int half = rd / 2;
+    const int rc = IL ? rd / 8 : half / 8;
+    const int CR = rc + (hd - rd) / 8;
+    const int nh = nq + 2 * nkv;
+    const int b = blockIdx.y;
+    const int64_t ps = pos[b];
+    x += (int64_t)b * nh * hd;
+    q_out += (int64_t)b * nq * hd;
+    if (ps < 0 || ps >= lim) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err, 1);
+        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nq * hd / 8; i += gridDim.x * blockDim.x) {
+            const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            V8<u16>::st(q_out + 8 * i, z);
+        }
+        return;
+    }
+    const float* cb = cosb + ps * half;
+    const float* sb = sinb + ps * half;
+    const int lane = threadIdx.x & 63;
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
+    if (w >= 2 * nkv) {  // q heads
+        const int i = (w - 2 * nkv) * 64 + lane;
+        if (i < nq * CR) {
+            const int h = i / CR, c = i - h * CR;
+            float o0[8], o1[8];
+            int e0, e1;
+            append_chunk<u16, IL>(x + (int64_t)h * hd, c, rc, half, rd, cb, sb, o0, o1, e0, e1);
+            V8<u16>::st(q_out + (int64_t)h * hd + e0, o0);
+            if (e1 >= 0) V8<u16>::st(q_out + (int64_t)h * hd + e1, o1);
+        }
+        return;
+    }
+    const bool isv = w >= nkv;
+    const int hk = isv ? w - nkv : w;
+    const u16* xr = x + (int64_t)(nq + w) * hd;  // heads are ordered q | k | v
+    float o0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, o1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int e0 = -1, e1 = -1;
+    if (isv) {
+        if (lane < hd / 8) {
+            e0 = 8 * lane;
+            V8<u16>::ld(xr + e0, o0);
+        }
+    } else if (lane < CR) {
+        append_chunk<u16, IL>(xr, lane, rc, half, rd, cb, sb, o0, o1, e0, e1);
+    }
+    bool bad = false;
+    float am = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        o0[j] = kv_finite_bf(o0[j], bad);
+        o1[j] = kv_finite_bf(o1[j], bad);
+        am = fmaxf(am, fmaxf(fabsf(o0[j]), fabsf(o1[j])));
+    }
+    am = wave_max(am);
+    const uint32_t bits = __float_as_uint(am);
+    const int E = (int)(bits >> 23);
+    int es = (bits & 0x7fffffu) <= 0x600000u ? E - 135 : E - 134;
+    if (es < -100) es = -100;  // covers the subnormal amax (E == 0)
+    const float s = bits == 0u ? 1.f : __uint_as_float((uint32_t)(es + 127) << 23);
+    const float inv = bits == 0u ? 1.f : __uint_as_float((uint32_t)(127 - es) << 23);
+    const int64_t row = (int64_t)b * cap + ps;
+    uint8_t* orow = (isv ? vc : kc) + (row * nkv + hk) * hd;
+    if (e0 >= 0) *reinterpret_cast<uint2*>(orow + e0) = e4m3_pack8(o0, inv);
+    if (e1 >= 0) *reinterpret_cast<uint2*>(orow + e1) = e4m3_pack8(o1, inv);
+    if (lane == 0) (isv ? v_scale : k_scale)[(int64_t)hk * s_head + row] = s;
+    if (__any(bad) && lane == 0) atomicOr(err, 2);
+#endif
 }
 
 static int grid_for(int64_t n) {
@@ -246,9 +365,19 @@ static int grid_for(int64_t n) {
 namespace sa_launch {
 bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, void* kc, void* vc, const int64_t* pos,
                     const float* cosb, const float* sinb, int nq, int nkv, int hd, int rd, int64_t lim, int* err,
-                    hipStream_t st, int B, int64_t cap) {
+                    hipStream_t st, int B, int64_t cap, float* k_scale, float* v_scale, int64_t s_head) {
     if (dtype == DT_F32 || hd % 8 || (interleaved ? rd % 8 : rd % 16) || B < 1 || B > 65535) return false;
     const int CR = (interleaved ? rd / 8 : rd / 16) + (hd - rd) / 8;
+    if (k_scale != nullptr) {  // FP8 cache: one wave per k / v head, then the q chunks
+        if (dtype != DT_BF16 || v_scale == nullptr || hd > 512) return false;
+        const dim3 g((2 * nkv + (nq * CR + 63) / 64 + 3) / 4, B);
+#define SA_RKV8(IL)                                                                                                 \
+    hipLaunchKernelGGL((rope_kv_append_q8_kernel<IL>), g, 256, 0, st, (const u16*)x, (u16*)q_out, (uint8_t*)kc,      \
+                       (uint8_t*)vc, k_scale, v_scale, s_head, pos, cosb, sinb, nq, nkv, hd, rd, lim, cap, err)
+        if (interleaved) SA_RKV8(true); else SA_RKV8(false);
+#undef SA_RKV8
+        return true;
+    }
     const dim3 g(grid_for((int64_t)(nq + 2 * nkv) * CR), B);
 #define SA_RKV(TT, IL)                                                                                            \
     hipLaunchKernelGGL((rope_kv_append_kernel<TT, IL>), g, 256, 0, st, (const TT*)x, (TT*)q_out, (TT*)kc, (TT*)vc, \

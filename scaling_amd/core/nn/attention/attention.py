@@ -22,6 +22,7 @@ from typing import Any, Callable, Optional, Sequence, Union
 import torch
 
 from ....ops import attention as attn_ops
+from ....ops import quant as quant_ops
 from ....ops._ext import ext, use_native
 from ....ops.gemm import decode_kernel, decode_rows_limit
 from ...topology import Topology
@@ -174,6 +175,19 @@ class KVCache:
         return self.k[: self.length], self.v[: self.length]
 
 
+KV_CACHE_SCHEMES = (quant_ops.SCHEME,)
+# error-word bit 1 (bit 0: a position outside the cache), set by the FP8 cache's append
+_NONFINITE_KV = ("FP8 KV cache: a step produced a K/V value that is NaN or above 2^127 in magnitude (infinity included); "
+                 "it was stored as 0 (NaN) or +-2^127 instead of a code that decodes to NaN or infinity")
+
+
+def check_kv_cache_scheme(kv_cache: Optional[str], who: str) -> Optional[str]:
+    """Validates a ``kv_cache=`` argument (None: the bf16 cache)."""
+    if kv_cache is not None and kv_cache not in KV_CACHE_SCHEMES:
+        raise ValueError(f"{who}: unknown kv_cache scheme {kv_cache!r} (supported: {', '.join(map(repr, KV_CACHE_SCHEMES))})")
+    return kv_cache
+
+
 class DecodeState:
     """Device-resident position of a graph-captured decode loop, shared by every layer's ``StaticKVCache``:
     ``pos`` [1] int64 is the position (= cache row) of the token being fed, ``cu_k`` [2] int32 = [0, pos + 1] the
@@ -192,9 +206,12 @@ class DecodeState:
 
     def check(self) -> None:
         """Raises if a decode step ran at a position outside its cache (one host read of the error word)."""
-        if int(self.err.item()) != 0:
+        e = int(self.err.item())
+        if e & 1 or e & ~3:
             raise RuntimeError("graph decode: a step's position exceeded the static KV cache or the rotary table; "
                                "its K/V rows were not written")
+        if e & 2:
+            raise RuntimeError(_NONFINITE_KV)
 
     def advance(self) -> None:
         self.pos.add_(1)
@@ -254,9 +271,12 @@ class BatchDecodeState:
 
     def check(self) -> None:
         """Raises if a decode step ran a sequence at a position outside its slab or the rotary table."""
-        if int(self.err.item()) != 0:
+        e = int(self.err.item())
+        if e & 1 or e & ~3:
             raise RuntimeError("batched decode: a sequence's position exceeded its static KV cache slab or the rotary "
                                "table; its K/V rows were not written")
+        if e & 2:
+            raise RuntimeError(_NONFINITE_KV)
 
     def advance(self) -> None:
         self.pos.add_(1)
@@ -299,6 +319,138 @@ class BatchStaticKVCache:
         self.v.index_copy_(0, rows, torch.where(keep, self.v.index_select(0, rows), v))
         st.err.bitwise_or_(bad.any().to(torch.int32))
         return self.k, self.v, st.k_range
+
+
+def _check_kv_dtype(dtype: torch.dtype, on_gpu: bool, who: str) -> None:
+    """The one dtype rule of the FP8 KV cache: bfloat16, or float32 off the GPU (rounded to bfloat16 first)."""
+    if dtype == torch.float16:
+        raise ValueError(f"{who}: bfloat16 models only (got float16: an e4m3 code times its power-of-two scale is "
+                         "exact in bfloat16 but can leave the float16 range)")
+    if dtype != torch.bfloat16 and not (dtype == torch.float32 and not on_gpu):
+        raise ValueError(f"{who}: bfloat16 models only (got {dtype}; float32 is taken on the CPU path alone, with K/V "
+                         "rounded to bfloat16 first)")
+
+
+class _FP8Rows:
+    """What the two FP8 caches share: the buffers of the format, their exact bf16 meaning and their size."""
+
+    k: torch.Tensor
+    v: torch.Tensor
+
+    def _set_scales(self, k_scale: torch.Tensor, v_scale: torch.Tensor, dtype: torch.dtype) -> None:
+        k, v = self.k, self.v
+        assert k.dtype == torch.uint8 and v.dtype == torch.uint8 and tuple(k_scale.shape) == (k.shape[1], k.shape[0])
+        self.k_scale, self.v_scale, self.dtype = k_scale, v_scale, dtype
+
+    @staticmethod
+    def _empty(rows: int, like: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """Codes (0) and scales (1) of ``rows`` unused rows shaped after ``like [*, nkv, hd]``."""
+        nkv, hd = like.shape[1], like.shape[2]
+        return (torch.zeros((rows, nkv, hd), dtype=torch.uint8, device=like.device),
+                torch.ones((nkv, rows), dtype=torch.float32, device=like.device))
+
+    @staticmethod
+    def _fill(codes: torch.Tensor, scale: torch.Tensor, at: int, src: torch.Tensor) -> None:
+        q, s = quant_ops.quantize_kv_rows(src.to(torch.bfloat16))
+        codes[at : at + src.shape[0]].copy_(q)
+        scale[:, at : at + src.shape[0]].copy_(s)
+
+    @property
+    def scales(self) -> tuple[torch.Tensor, torch.Tensor]:
+        return self.k_scale, self.v_scale
+
+    def dequantized(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """The bf16 K and V buffers this cache encodes (exactly)."""
+        return (quant_ops.dequantize_kv_rows(self.k, self.k_scale), quant_ops.dequantize_kv_rows(self.v, self.v_scale))
+
+    def bytes_per_token(self) -> int:
+        return 2 * self.k.shape[1] * (self.k.shape[2] + 4)
+
+
+class StaticKVCacheFP8(_FP8Rows, StaticKVCache):
+    """``StaticKVCache`` holding OCP e4m3fn codes: scheme ``"fp8_e4m3"`` of ``ops/quant.py``, one row = one token of
+    one kv head.  ``k`` / ``v`` are uint8 ``[cap, nkv, hd]`` (one byte per element) and ``k_scale`` / ``v_scale``
+    fp32 ``[nkv, cap]`` -- head-major, so the four consecutive keys of an accumulator register group of the decode
+    kernel's 32x32 MFMA are one 16-byte load --, one power-of-two scale per row: ``hd + 4`` bytes per token, head and
+    tensor instead of ``2 hd``.  Codes and scale of a row are ``ops.quant.quantize_rows_fp8`` of the bf16 row the bf16
+    cache would hold (after RoPE, after rounding to bf16), so the cache is an exact encoding of a bf16 cache
+    (``dequantized()``) and only the rounding of K/V to e4m3 changes the model.  Unused rows hold code 0, scale 1.
+
+    ``from_cache`` quantises the rows the prefill left: the prompt itself was prefilled against exact bf16 K/V, and
+    only the decode steps read the quantised rows.  ``append`` is the unfused write (CPU, fallbacks); it gives the
+    codes and scales of the fused kernel (``ext().rope_kv_append`` with scales).  The one exception to exactness: a
+    NaN is stored as 0 and a magnitude above 2^127 (infinity included) as +-2^127 -- the top of that range would
+    round to a code whose product with the scale is infinite --; either sets bit 1 of the state's error word."""
+
+    def __init__(self, k: torch.Tensor, v: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                 state: DecodeState, dtype: torch.dtype) -> None:
+        StaticKVCache.__init__(self, k, v, state)
+        self._set_scales(k_scale, v_scale, dtype)
+
+    @classmethod
+    def from_cache(cls, kv: "KVCache", capacity: int, state: DecodeState) -> "StaticKVCacheFP8":  # type: ignore[override]
+        n = kv.length
+        assert capacity >= n, (capacity, n)
+        _check_kv_dtype(kv.k.dtype, kv.k.is_cuda, "StaticKVCacheFP8")
+        (kb, ks), (vb, vs) = cls._empty(capacity, kv.k), cls._empty(capacity, kv.v)
+        cls._fill(kb, ks, 0, kv.k[:n])
+        cls._fill(vb, vs, 0, kv.v[:n])
+        return cls(kb, vb, ks, vs, state, kv.k.dtype)
+
+    def append(self, k: torch.Tensor, v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        assert k.shape[0] == 1, "graph-captured decoding feeds one token per step"
+        st = self.state
+        for codes, scale, x in ((self.k, self.k_scale, k), (self.v, self.v_scale, v)):
+            xb, bad = quant_ops.sanitize_kv(x)
+            q, s = quant_ops.quantize_kv_rows(xb, check=False)
+            codes.index_copy_(0, st.pos, q)
+            scale.index_copy_(1, st.pos, s)
+            st.err.bitwise_or_(bad.to(torch.int32) * 2)
+        return self.k, self.v, st.cu_k
+
+
+class BatchStaticKVCacheFP8(_FP8Rows, BatchStaticKVCache):
+    """``BatchStaticKVCache`` in the format of ``StaticKVCacheFP8``: codes uint8 ``[B * cap, nkv, hd]``, scales fp32
+    ``[nkv, B * cap]`` (head-major), the same slabs.  ``from_caches`` quantises the prefilled rows (the prompts were
+    prefilled against exact bf16 K/V); ``append`` is the unfused write, equal to the fused kernel's codes and scales."""
+
+    def __init__(self, k: torch.Tensor, v: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                 state: BatchDecodeState, dtype: torch.dtype) -> None:
+        BatchStaticKVCache.__init__(self, k, v, state)
+        self._set_scales(k_scale, v_scale, dtype)
+
+    @classmethod
+    def from_caches(cls, kvs: Sequence["KVCache"], state: BatchDecodeState) -> "BatchStaticKVCacheFP8":  # type: ignore[override]
+        cap = state.capacity
+        assert len(kvs) == state.batch
+        k0 = kvs[0].k
+        _check_kv_dtype(k0.dtype, k0.is_cuda, "BatchStaticKVCacheFP8")
+        (kb, ks), (vb, vs) = cls._empty(len(kvs) * cap, k0), cls._empty(len(kvs) * cap, k0)
+        for b, kv in enumerate(kvs):
+            n = kv.length
+            assert n <= cap, (n, cap)
+            cls._fill(kb, ks, b * cap, kv.k[:n])
+            cls._fill(vb, vs, b * cap, kv.v[:n])
+        return cls(kb, vb, ks, vs, state, k0.dtype)
+
+    def append(self, k: torch.Tensor, v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The unfused write of one token per sequence; out-of-range positions as ``BatchStaticKVCache.append``."""
+        st = self.state
+        assert k.shape[0] == st.batch, "batched decoding feeds one token per sequence and step"
+        bad = (st.pos < 0) | (st.pos >= st.capacity)
+        rows = st.row_base + st.pos.clamp(0, st.capacity - 1)
+        for codes, scale, x in ((self.k, self.k_scale, k), (self.v, self.v_scale, v)):
+            xb, nonfinite = quant_ops.sanitize_kv(x)
+            q, s = quant_ops.quantize_kv_rows(xb, check=False)
+            codes.index_copy_(0, rows, torch.where(bad.view(-1, 1, 1), codes.index_select(0, rows), q))
+            scale.index_copy_(1, rows, torch.where(bad.view(1, -1), scale.index_select(1, rows), s))
+            st.err.bitwise_or_(nonfinite.to(torch.int32) * 2)
+        st.err.bitwise_or_(bad.any().to(torch.int32))
+        return self.k, self.v, st.k_range
+
+
+def _fp8_scales(kv: Any) -> Optional[tuple[torch.Tensor, torch.Tensor]]:
+    return kv.scales if isinstance(kv, (StaticKVCacheFP8, BatchStaticKVCacheFP8)) else None
 
 
 class _LoraUpInto(torch.autograd.Function):
@@ -548,6 +700,8 @@ class ParallelSelfAttention(torch.nn.Module):
         re = self.rotary_embedding
         if not (isinstance(kv, StaticKVCache) and re is not None and re.interleaved and self.use_flash_attention):
             return None
+        if _fp8_scales(kv) is not None:  # gemv_norm_rope writes bf16 cache rows itself: no FP8 form
+            return None
         if position_ids is None or position_ids.numel() != 1 or position_ids.data_ptr() != kv.state.pos.data_ptr():
             return None
         q = ext().gemv_norm_rope(x2, nw[0], nw[1], w, re.cos_table, re.sin_table, kv.state.pos,
@@ -632,6 +786,20 @@ class ParallelSelfAttention(torch.nn.Module):
                 value = value + out
         return [query, key, value]
 
+    def check_fp8_kv_cache(self) -> None:
+        """Raises ``ValueError`` naming the restriction if this layer cannot decode over an FP8 KV cache (the decoders
+        call it once per layer, before anything is prefilled or quantised)."""
+        if not self.use_flash_attention:
+            raise ValueError("FP8 KV cache: the torch (non-flash) attention kernel is not supported; set "
+                             "masked_softmax.kernel to 'flash_attention'")
+        if self.key_query_norm:
+            raise ValueError("FP8 KV cache: key_query_norm is not supported (the fused append rotates the projection's "
+                             "k heads directly)")
+        if self.topology is not None and self.topology.config.model_parallel_size > 1:
+            raise ValueError("FP8 KV cache: tensor parallelism (model_parallel_size > 1) is not supported")
+        p = next(self.parameters())
+        _check_kv_dtype(p.dtype, p.is_cuda, "FP8 KV cache")
+
     def _decode_rope_append(self, base: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                             position_ids: Optional[torch.Tensor], cache_index: int) -> Optional[tuple]:
         """One-token step of graph-captured decoding: rotate q and k and append k/v at the cache's device-side
@@ -652,8 +820,9 @@ class ParallelSelfAttention(torch.nn.Module):
                 and k.data_ptr() == base.data_ptr() + nq * hd * es and v.data_ptr() == base.data_ptr() + (nq + nkv) * hd * es
                 and q.stride(1) == hd and k.stride(1) == hd and v.stride(1) == hd):
             return None
+        sc = _fp8_scales(kv) or (None, None)
         qr = ext().rope_kv_append(base.view(1, nq + 2 * nkv, hd), re.cos_table, re.sin_table, kv.state.pos, nq, nkv,
-                                  re.dimensions, re.interleaved, kv.k, kv.v, kv.state.err)
+                                  re.dimensions, re.interleaved, kv.k, kv.v, kv.state.err, sc[0], sc[1])
         if qr is None:
             return None
         return qr, kv.k, kv.v, kv.state.cu_k
@@ -677,8 +846,9 @@ class ParallelSelfAttention(torch.nn.Module):
                 and v.data_ptr() == base.data_ptr() + (nq + nkv) * hd * es
                 and all(t.stride(1) == hd and (st.batch == 1 or t.stride(0) == nh * hd) for t in (q, k, v))):
             return None
+        sc = _fp8_scales(kv) or (None, None)
         qr = ext().rope_kv_append_batch(base.view(st.batch, nh, hd), re.cos_table, re.sin_table, st.pos, nq, nkv,
-                                        re.dimensions, re.interleaved, kv.k, kv.v, st.err, st.capacity)
+                                        re.dimensions, re.interleaved, kv.k, kv.v, st.err, st.capacity, sc[0], sc[1])
         if qr is None:
             return None
         return qr, kv.k, kv.v, st.k_range
@@ -712,6 +882,8 @@ class ParallelSelfAttention(torch.nn.Module):
         batch_kv = self.cache.get(cache_index) if use_cache and not reset_cache else None
         if not isinstance(batch_kv, BatchStaticKVCache):
             batch_kv = None
+        # FP8 static cache (decode steps only): k / v below are its codes, read with these scales
+        kv_scales = _fp8_scales(self.cache.get(cache_index)) if use_cache and not reset_cache else None
         probe("attention.input", x)
         if projected_step is not None:  # graph decode: norm + q/k/v GEMV + RoPE + K/V append were one launch
             q, k, v, cumulative_seq_lengths_key = projected_step
@@ -789,6 +961,8 @@ class ParallelSelfAttention(torch.nn.Module):
                 assert s == 1 and b == batch_kv.state.batch, "batched decoding feeds one token per sequence"
                 common.update(cu_seqlens_k=None, key_ranges=cumulative_seq_lengths_key,
                               max_seqlen_k=batch_kv.state.capacity)
+            if kv_scales is not None:
+                common.update(kv_scales=kv_scales)
             hidden = attn_ops.flash_attention(q, k, v, window=window, **common,
                                               local_heads=self.num_local_attention_heads_per_partition if nl > 0 else None)
             hidden = hidden.reshape(b, s, -1)

@@ -334,6 +334,56 @@ def _flash_attention_ranges(q, k, v, cu_seqlens_q, key_ranges, max_seqlen_q, max
     return o
 
 
+def _flash_attention_fp8_kv(q, k, v, kv_scales, cu_seqlens_q, cu_seqlens_k, key_ranges, max_seqlen_q, max_seqlen_k,
+                            softmax_scale, causal, window, p_drop, local_heads) -> torch.Tensor:
+    """:func:`flash_attention` with ``kv_scales``: the flash-decoding kernel over FP8 K/V, or -- off the GPU -- the
+    dense reference on the dequantised K/V."""
+    from .quant import dequantize_kv_rows
+
+    k_scale, v_scale = kv_scales
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    win = -1 if window is None else int(window)
+    if p_drop > 0.0:
+        raise ValueError("flash attention: FP8 K/V (kv_scales) does not support dropout")
+    if torch.is_grad_enabled() and q.requires_grad:
+        raise ValueError("flash attention: FP8 K/V (kv_scales) is forward only (run under torch.no_grad())")
+    for t in (k, v):
+        if t.dtype not in (torch.uint8, torch.float8_e4m3fn):
+            raise ValueError(f"flash attention: with kv_scales, k and v must be uint8 / float8_e4m3fn codes, got {t.dtype}")
+    for t, sc in ((k, k_scale), (v, v_scale)):
+        if sc.dtype != torch.float32 or tuple(sc.shape) != (t.shape[1], t.shape[0]):
+            raise ValueError(f"flash attention: kv_scales must be float32 [kv heads, key rows] = "
+                             f"{(t.shape[1], t.shape[0])}, got {sc.dtype} {tuple(sc.shape)}")
+    if key_ranges is None and cu_seqlens_k is None:
+        raise ValueError("flash attention: FP8 K/V (kv_scales) needs cu_seqlens_k or key_ranges")
+    if not use_native(q):
+        if q.dtype == torch.float16:
+            raise ValueError("flash attention: FP8 K/V (kv_scales) needs bfloat16 queries, got torch.float16")
+        kd, vd = dequantize_kv_rows(k, k_scale, q.dtype), dequantize_kv_rows(v, v_scale, q.dtype)
+        return attention_reference(q, kd, vd, cu_seqlens_q, cu_seqlens_k, scale, causal, win, local_heads=local_heads,
+                                   key_ranges=key_ranges)
+    if q.dtype != torch.bfloat16:
+        raise ValueError(f"flash attention: FP8 K/V (kv_scales) needs bfloat16 queries, got {q.dtype}")
+    cq = cu_seqlens_q.to(torch.int32)
+    if max_seqlen_q is None:
+        max_seqlen_q = int((cq[1:] - cq[:-1]).max().item())
+    if int(max_seqlen_q) * (q.shape[1] // k.shape[1]) > 32:
+        raise ValueError("flash attention: FP8 K/V (kv_scales) is supported by the decode kernel only "
+                         "(max_seqlen_q * q heads per kv head <= 32)")
+    if key_ranges is not None:
+        if max_seqlen_k is None:
+            raise ValueError("flash attention: key_ranges need max_seqlen_k (the per-sequence capacity)")
+        ck = cq
+    else:
+        ck = cu_seqlens_k.to(torch.int32)
+        if max_seqlen_k is None:
+            max_seqlen_k = int((ck[1:] - ck[:-1]).max().item())
+    lh = -1 if local_heads is None else int(local_heads)
+    o, _ = ext().fa_fwd(q, k, v, cq, ck, int(max_seqlen_q), float(scale), bool(causal), win, 0.0, 0, lh,
+                        int(max_seqlen_k), key_ranges, k_scale, v_scale)
+    return o
+
+
 def flash_attention(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -350,6 +400,7 @@ def flash_attention(
     local_heads: Optional[int] = None,
     deterministic: bool = True,
     key_ranges: Optional[torch.Tensor] = None,
+    kv_scales: Optional[tuple[torch.Tensor, torch.Tensor]] = None,
 ) -> torch.Tensor:
     """q: [T, Hq, D]; k, v: [Tk, Hk, D] (unit last stride); cu_seqlens int32 [nseg+1].
 
@@ -360,7 +411,16 @@ def flash_attention(
     instead of [cu_seqlens_k[i], cu_seqlens_k[i + 1]) -- a batched static KV cache keeps one fixed-capacity slab per
     sequence, so the keys are not packed back to back.  ``cu_seqlens_k`` is then ignored and ``max_seqlen_k`` (the
     per-sequence capacity; it sizes the split plan) is required.  Decode-sized calls only (max_seqlen_q * q heads per
-    kv head <= 32, no dropout), forward only: anything else raises."""
+    kv head <= 32, no dropout), forward only: anything else raises.
+
+    ``kv_scales`` = (k_scale, v_scale), float32 [Hk, Tk]: FP8 K/V.  ``k`` / ``v`` then hold OCP e4m3fn codes (uint8 or
+    float8_e4m3fn) and row t of kv head h means ``code * scale[h, t]`` (``ops.quant.quantize_kv_rows``), with either
+    key form.  bfloat16 queries, decode-sized calls, no dropout, forward only: anything else raises ``ValueError``.
+    The result is bit for bit the bf16 kernel's on the dequantised K/V; on CPU tensors the reference runs on them."""
+    if kv_scales is not None:
+        return _flash_attention_fp8_kv(q, k, v, kv_scales, cu_seqlens_q, cu_seqlens_k, key_ranges, max_seqlen_q,
+                                       max_seqlen_k, softmax_scale, causal, window,
+                                       dropout_p if training else 0.0, local_heads)
     if key_ranges is not None:
         return _flash_attention_ranges(q, k, v, cu_seqlens_q, key_ranges, max_seqlen_q, max_seqlen_k, softmax_scale,
                                        causal, window, dropout_p if training else 0.0, local_heads)

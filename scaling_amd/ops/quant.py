@@ -40,6 +40,11 @@ def quantize_rows_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     wf = w.detach().float()
     if not bool(torch.isfinite(wf).all()):
         raise ValueError("quantize_rows_fp8: the weight holds non-finite values")
+    return _quantize_rows(wf)
+
+
+def _quantize_rows(wf: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The arithmetic of ``quantize_rows_fp8`` on a finite fp32 matrix (device ops only, no host read)."""
     amax = wf.abs().amax(dim=1) if wf.shape[1] > 0 else wf.new_zeros(wf.shape[0])
     zero = amax == 0
     # amax / 448 = m * 2^e with m in [0.5, 1): ceil(log2) is e, or e - 1 when m is exactly 0.5
@@ -60,6 +65,47 @@ def dequantize_rows_fp8(q: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype
     if q.dtype == torch.uint8:
         q = q.view(torch.float8_e4m3fn)
     return (q.float() * scale.float()[:, None]).to(dtype)
+
+
+# The largest K/V magnitude the cache format takes.  A row with amax in (240 * 2^120, bf16 max] would round amax to the
+# code of 256 at scale 2^120, and 256 * 2^120 = 2^128 is infinite in bf16; the cut sits at the power of two below.
+KV_MAX = 2.0 ** 127
+
+
+def quantize_kv_rows(x: torch.Tensor, check: bool = True) -> tuple[torch.Tensor, torch.Tensor]:
+    """K or V cache rows ``x [rows, nkv, hd]`` in the FP8 cache format: ``(codes [rows, nkv, hd] uint8, scale
+    [nkv, rows] fp32)``.  A row of the format is one token of one kv head: its codes and scale are exactly
+    ``quantize_rows_fp8`` of that row viewed as ``[1, hd]`` (e4m3fn codes, one power-of-two scale).  The scales are
+    head-major, the layout of the cache and of the decode kernel.  Works on CPU and GPU tensors.
+
+    ``check=False`` skips the finiteness test (a host read): the caller has replaced non-finite values."""
+    if x.dim() != 3:
+        raise ValueError(f"quantize_kv_rows: expected [rows, nkv, hd], got shape {tuple(x.shape)}")
+    rows, nkv, hd = x.shape
+    flat = x.detach().reshape(rows * nkv, hd)
+    q, s = quantize_rows_fp8(flat) if check else _quantize_rows(flat.float())
+    return q.view(torch.uint8).view(rows, nkv, hd), s.view(rows, nkv).t().contiguous()
+
+
+def dequantize_kv_rows(codes: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """``[rows, nkv, hd]`` values of ``quantize_kv_rows`` output (codes uint8 or float8_e4m3fn, scale ``[nkv, rows]``);
+    exact in bf16 and fp32."""
+    if codes.dim() != 3 or tuple(scale.shape) != (codes.shape[1], codes.shape[0]):
+        raise ValueError(f"dequantize_kv_rows: codes {tuple(codes.shape)} need scales [nkv, rows], got {tuple(scale.shape)}")
+    rows, nkv, hd = codes.shape
+    flat = dequantize_rows_fp8(codes.reshape(rows * nkv, hd), scale.t().reshape(rows * nkv), dtype)
+    return flat.view(rows, nkv, hd)
+
+
+def sanitize_kv(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """``x`` as bf16 with NaN -> 0 and every magnitude above ``KV_MAX`` (2^127; infinity included) -> +-2^127 -- what
+    the FP8 append kernel stores, so that the largest code times the row's scale stays finite --, and a 0-d bool
+    tensor: whether anything was replaced.  Device ops only."""
+    xb = x.detach().to(torch.bfloat16)
+    nan = torch.isnan(xb)
+    big = xb.abs() > KV_MAX
+    xb = torch.where(nan, torch.zeros_like(xb), xb.clamp(-KV_MAX, KV_MAX))
+    return xb, (nan | big).any()
 
 
 def attach_w8(param: torch.Tensor, q: torch.Tensor, scale: torch.Tensor) -> None:

@@ -34,7 +34,8 @@ from typing import Any, Callable, Optional, Sequence
 import torch
 
 from ...ops import gemm as gemm_ops
-from ...core.nn.attention.attention import BatchDecodeState, BatchStaticKVCache, KVCache, ParallelSelfAttention
+from ...core.nn.attention.attention import (BatchDecodeState, BatchStaticKVCache, BatchStaticKVCacheFP8, KVCache,
+                                            ParallelSelfAttention, check_kv_cache_scheme)
 from ..data import TextDatasetBatch
 from ..data.inference_settings import InferenceSettings
 
@@ -45,13 +46,19 @@ class BatchDecoder:
     ``tok`` ``[B, 1]`` int64 is the static token buffer a step feeds and then overwrites with the tokens it sampled.
     A caller may overwrite it between steps (teacher forcing, a serving loop that substitutes tokens).
     ``tokens`` ``[max_tokens, B]`` and ``logits`` ``[max_tokens, B, V]`` record every step; row 0 of both is the
-    prefill's."""
+    prefill's.
+
+    ``kv_cache="fp8_e4m3"`` (opt-in): the batched cache holds e4m3 codes with one power-of-two scale per cached row
+    (``BatchStaticKVCacheFP8``: the prefilled rows are quantised here, every step appends quantised rows and the
+    flash-decoding kernel reads the codes).  It touches attention only, so it composes with FP8 weights and
+    ``skinny_gemm``."""
 
     def __init__(self, module: Any, prompt_lengths: Sequence[int], max_tokens: int, first_tokens: torch.Tensor,
                  sample_fn: Callable[[torch.Tensor], torch.Tensor], prefill_logits: torch.Tensor,
-                 skinny_gemm: bool = False) -> None:
+                 skinny_gemm: bool = False, kv_cache: Optional[str] = None) -> None:
         self.module = module
         self.skinny_gemm = bool(skinny_gemm)
+        self.kv_cache = check_kv_cache_scheme(kv_cache, "BatchDecoder")
         dev = first_tokens.device
         B = len(prompt_lengths)
         assert B >= 1 and max_tokens >= 1 and first_tokens.numel() == B and prefill_logits.shape[0] == B
@@ -62,13 +69,17 @@ class BatchDecoder:
         self.state = BatchDecodeState(prompt_lengths, self.capacity, dev)
         self.attns = [m for m in module.modules() if isinstance(m, ParallelSelfAttention)]
         assert self.attns, "no attention layers"
+        cache_cls = BatchStaticKVCache if self.kv_cache is None else BatchStaticKVCacheFP8
+        if self.kv_cache is not None:
+            for a in self.attns:
+                a.check_fp8_kv_cache()
         for a in self.attns:
             kvs = [a.cache.get(b) for b in range(B)]
             assert all(isinstance(kv, KVCache) for kv in kvs), "batched decoding starts from B prefilled KV caches"
             assert [kv.length for kv in kvs] == list(prompt_lengths)
             for b in range(1, B):
                 del a.cache[b]
-            a.cache[0] = BatchStaticKVCache.from_caches(kvs, self.state)
+            a.cache[0] = cache_cls.from_caches(kvs, self.state)
         V = prefill_logits.shape[-1]
         rows = max(max_tokens, 2)  # the warm-up / capture passes record a step 1 even when max_tokens is 1
         self.first = first_tokens.reshape(B, 1).to(torch.long).clone()

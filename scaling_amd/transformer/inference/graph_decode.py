@@ -25,7 +25,8 @@ from typing import Any, Callable, Optional, Sequence
 
 import torch
 
-from ...core.nn.attention.attention import DecodeState, KVCache, ParallelSelfAttention, StaticKVCache
+from ...core.nn.attention.attention import (DecodeState, KVCache, ParallelSelfAttention, StaticKVCache,
+                                            StaticKVCacheFP8, check_kv_cache_scheme)
 from ..data import TextDatasetBatch
 from ..data.inference_settings import InferenceSettings
 
@@ -33,8 +34,11 @@ from ..data.inference_settings import InferenceSettings
 class GraphDecoder:
     def __init__(self, module: Any, n_prompt: int, max_tokens: int, first_token: torch.Tensor,
                  sample_fn: Callable[[torch.Tensor], torch.Tensor], vocab_logits: torch.Tensor,
-                 cache_index: int = 0) -> None:
+                 cache_index: int = 0, kv_cache: Optional[str] = None) -> None:
+        """``kv_cache="fp8_e4m3"``: the static caches hold e4m3 codes with one power-of-two scale per cached row
+        (``StaticKVCacheFP8``; the prefilled rows are quantised here); None: bf16 caches."""
         self.module = module
+        self.kv_cache = check_kv_cache_scheme(kv_cache, "GraphDecoder")
         dev = first_token.device
         self.n_prompt = n_prompt
         self.max_tokens = max_tokens
@@ -42,10 +46,14 @@ class GraphDecoder:
         self.attns = [m for m in module.modules() if isinstance(m, ParallelSelfAttention)]
         assert self.attns, "no attention layers"
         capacity = n_prompt + max_tokens
+        cache_cls = StaticKVCache if self.kv_cache is None else StaticKVCacheFP8
+        if self.kv_cache is not None:
+            for a in self.attns:
+                a.check_fp8_kv_cache()
         for a in self.attns:
             kv = a.cache.get(cache_index)
             assert isinstance(kv, KVCache), "graph decoding starts from a prefilled KV cache"
-            a.cache[cache_index] = StaticKVCache.from_cache(kv, capacity, self.state)
+            a.cache[cache_index] = cache_cls.from_cache(kv, capacity, self.state)
         self.first = first_token.reshape(1, 1).to(torch.long)
         self.tok = self.first.clone()
         self.tokens = torch.zeros(max_tokens, dtype=torch.long, device=dev)

@@ -179,14 +179,24 @@ class TransformerInferenceModule(InferenceModule):
     def generate(self, max_tokens: int, input_text: Optional[str] = None, input_tokens: Optional[list[int]] = None,
                  sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                  stop_tokens: Optional[Sequence[int]] = None, use_cache: bool = True,
-                 use_cuda_graph: bool = False) -> CompletionOutput:
+                 use_cuda_graph: bool = False, kv_cache: Optional[str] = None) -> CompletionOutput:
         """Completion text / tokens / logits for a prompt.  With the KV cache each step feeds only the new
         token (with its absolute position); without it the whole sequence is re-run.
 
         ``use_cuda_graph`` (KV cache, one GPU, flash attention, a graph-safe sampler: ``sample_argmax`` or
         ``sample.Sampler``): after the prefill, the decode step is captured once as a HIP graph and replayed per token
         (``graph_decode.GraphDecoder``) — same kernels and results as the eager loop, without its per-token
-        launch and Python overhead."""
+        launch and Python overhead.
+
+        ``kv_cache="fp8_e4m3"`` (opt-in, with ``use_cuda_graph`` only): the decode steps keep K/V as e4m3 codes with
+        one power-of-two scale per cached row (see ``generate_batch``).  The eager loop keeps its growing bf16 cache
+        and raises ``ValueError`` if the argument is given."""
+        from ...core.nn.attention.attention import check_kv_cache_scheme
+
+        check_kv_cache_scheme(kv_cache, "generate")
+        if kv_cache is not None and not use_cuda_graph:
+            raise ValueError("generate: kv_cache needs use_cuda_graph=True (the eager loop keeps a growing bf16 KV cache); "
+                             "generate_batch takes kv_cache with and without the graph")
         if stop_tokens is None:
             assert self.tokenizer is not None, "If no tokenizer is provided, a stop token needs to be set manually"
             stop_tokens = [self.tokenizer.eos_token_id]
@@ -197,7 +207,7 @@ class TransformerInferenceModule(InferenceModule):
         n_in = cur.input_token_ids.shape[-1]
         if use_cuda_graph:
             assert use_cache, "graph-captured decoding needs the KV cache"
-            return self._generate_graph(cur, n_in, max_tokens, sample_fn, stop_tokens)
+            return self._generate_graph(cur, n_in, max_tokens, sample_fn, stop_tokens, kv_cache=kv_cache)
         settings = InferenceSettings(use_cache=use_cache, reset_cache=not use_cache, cache_index=0, embedding_layers=[-1])
         tokens: list[int] = []
         step_logits: list[torch.Tensor] = []
@@ -226,13 +236,19 @@ class TransformerInferenceModule(InferenceModule):
 
     def batch_decoder(self, max_tokens: int, input_tokens: Sequence[Sequence[int]],
                       sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
-                      skinny_gemm: bool = False) -> Any:
+                      skinny_gemm: bool = False, kv_cache: Optional[str] = None) -> Any:
         """Prefills the prompts one at a time (prompt b under ``cache_index`` b), draws every row's first token with
         ONE ``sample_fn`` call on the stacked prefill logits and returns the ``batch_decode.BatchDecoder`` that decodes
         them together (not yet captured: call ``capture()`` for graph replay).  ``skinny_gemm``: its steps run inside
-        ``ops.gemm.skinny_gemm()`` (the MFMA weight-streaming kernels for up to 16 rows, see ``generate_batch``)."""
+        ``ops.gemm.skinny_gemm()`` (the MFMA weight-streaming kernels for up to 16 rows, see ``generate_batch``).
+        ``kv_cache``: None (bf16) or ``"fp8_e4m3"`` (see ``generate_batch``)."""
+        from ...core.nn.attention.attention import ParallelSelfAttention, check_kv_cache_scheme
         from .batch_decode import BatchDecoder
 
+        if check_kv_cache_scheme(kv_cache, "generate_batch") is not None:  # refuse before the prefills run
+            for m in self.modules():
+                if isinstance(m, ParallelSelfAttention):
+                    m.check_fp8_kv_cache()
         if len(input_tokens) == 0:
             raise ValueError("generate_batch: no prompts")
         if any(len(p) == 0 for p in input_tokens):
@@ -252,13 +268,14 @@ class TransformerInferenceModule(InferenceModule):
         prefill = torch.stack(last)  # [B, 1, V]
         first = sample_fn(prefill)
         return BatchDecoder(self, [len(p) for p in input_tokens], max_tokens, first, sample_fn, prefill,
-                            skinny_gemm=skinny_gemm)
+                            skinny_gemm=skinny_gemm, kv_cache=kv_cache)
 
     def generate_batch(self, max_tokens: int, input_texts: Optional[Sequence[str]] = None,
                        input_tokens: Optional[Sequence[Sequence[int]]] = None,
                        sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                        stop_tokens: Optional[Sequence[int]] = None,
-                       use_cuda_graph: bool = False, skinny_gemm: bool = False) -> list[CompletionOutput]:
+                       use_cuda_graph: bool = False, skinny_gemm: bool = False,
+                       kv_cache: Optional[str] = None) -> list[CompletionOutput]:
         """Completions for B prompts of any lengths, decoded together: one pass over the weights per step serves all
         B rows (``batch_decode.BatchDecoder``).  One device, always with the KV cache (flash attention kernel); the
         prompts are prefilled one at a time.  Stop tokens act per row: every row keeps stepping until all rows have
@@ -277,8 +294,18 @@ class TransformerInferenceModule(InferenceModule):
         kernels (``csrc/kernels/skinny.hip``; ``ops.gemm.skinny_gemm``), eager and graph alike, under the conditions of
         the GEMV paths (bf16 / fp16 model, optionally FP8 copies, one device, TP 1); ``use_cuda_graph`` then takes up to
         16 prompts.  Every row of those kernels is bitwise independent of the other rows.  The flag is inert off the
-        GPU, and above 16 rows the eager loop runs the library path as without it."""
+        GPU, and above 16 rows the eager loop runs the library path as without it.
+
+        ``kv_cache="fp8_e4m3"`` (opt-in; default None, the bf16 cache): the decode steps keep K/V as OCP e4m3 codes with
+        one fp32 power-of-two scale per cached row (one token of one kv head) -- ``hd + 4`` bytes instead of ``2 hd``
+        -- written by the quantising RoPE + append kernel and read by the flash-decoding kernel
+        (``BatchStaticKVCacheFP8``).  The prompts are prefilled against exact bf16 K/V and their rows quantised
+        afterwards.  bf16 models on one device with the flash attention kernel; fp16, tensor parallelism and
+        ``key_query_norm`` raise ``ValueError``.  It composes with ``quantize_weights`` and ``skinny_gemm``."""
+        from ...core.nn.attention.attention import check_kv_cache_scheme
         from ...ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS
+
+        check_kv_cache_scheme(kv_cache, "generate_batch")
 
         if (input_texts is None) == (input_tokens is None):
             raise ValueError("generate_batch: give either input_texts or input_tokens")
@@ -300,7 +327,7 @@ class TransformerInferenceModule(InferenceModule):
         if stop_tokens is None:
             assert self.tokenizer is not None, "If no tokenizer is provided, a stop token needs to be set manually"
             stop_tokens = [self.tokenizer.eos_token_id]
-        dec = self.batch_decoder(max_tokens, input_tokens, sample_fn, skinny_gemm=skinny_gemm)
+        dec = self.batch_decoder(max_tokens, input_tokens, sample_fn, skinny_gemm=skinny_gemm, kv_cache=kv_cache)
         if use_cuda_graph:
             dec.capture()
         outs = []
@@ -310,14 +337,20 @@ class TransformerInferenceModule(InferenceModule):
         return outs
 
     def _generate_graph(self, prompt: TextDatasetBatch, n_in: int, max_tokens: int,
-                        sample_fn: Callable[[torch.Tensor], torch.Tensor], stop_tokens: Sequence[int]) -> CompletionOutput:
+                        sample_fn: Callable[[torch.Tensor], torch.Tensor], stop_tokens: Sequence[int],
+                        kv_cache: Optional[str] = None) -> CompletionOutput:
+        from ...core.nn.attention.attention import ParallelSelfAttention
         from .graph_decode import GraphDecoder
 
         assert self.devices is not None and len(self.devices) == 1, "graph-captured decoding runs on one device"
+        if kv_cache is not None:  # refuse before the prefill runs
+            for m in self.modules():
+                if isinstance(m, ParallelSelfAttention):
+                    m.check_fp8_kv_cache()
         out = self.forward(prompt)  # prefill (reset_cache): fills each layer's KVCache
         first = sample_fn(out.activations)
         assert first.is_cuda, "graph-captured decoding needs a GPU"
-        dec = GraphDecoder(self, n_in, max_tokens, first, sample_fn, out.activations[:, -1, :])
+        dec = GraphDecoder(self, n_in, max_tokens, first, sample_fn, out.activations[:, -1, :], kv_cache=kv_cache)
         dec.capture()
         tokens, logits = dec.run(stop_tokens)
         text = self.tokenizer.decode(tokens) if self.tokenizer is not None else None

@@ -2,6 +2,7 @@
 
     python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64] [--sampler T,K,P | torch:T,K,P]
                                  [--weights fp8_e4m3 [--lm-head]] [--batch B [--skinny]]
+                                 [--kv-cache bf16,fp8_e4m3 [--rounds N]]
 
 ``--batch B`` times batched generation instead (``generate_batch`` / ``BatchDecoder``): B random prompts of lengths
 ``prompt, prompt - 7, prompt - 14, ...`` decoded together; ms per step, tokens/s summed over the rows, and (B <= 4:
@@ -11,6 +12,10 @@ the graph limit) the captured loop and ``graph_tokens_equal_eager``.  ``--skinny
 ``--weights fp8_e4m3`` decodes the model after ``quantize_weights()`` (FP8 weight-only decoding; ``--lm-head`` includes
 the LM head); ``weights_gib`` and ``graph_gb_per_s`` then count what one decode step streams (the FP8 copies in place of
 their bf16 parameters).
+
+``--kv-cache fp8_e4m3`` (with ``--batch``) decodes over the FP8 KV cache (``generate_batch(kv_cache=...)``); a comma
+list such as ``bf16,fp8_e4m3`` measures the settings alternately in this process, ``--rounds`` times, one JSON line
+each.  Every line carries ``kv_cache`` and ``kv_bytes_per_token`` (K and V of all layers).
 
 ``--sampler 0.8,40,0.95`` decodes with the fused ``Sampler`` (temperature, top-k, top-p) in both loops;
 ``--sampler torch:0.8,40,0.95`` times the eager loop with the torch composition
@@ -44,7 +49,13 @@ def main() -> None:
     p.add_argument("--lm-head", action="store_true", help="with --weights fp8_e4m3: quantise the LM head too")
     p.add_argument("--batch", type=int, default=0, help="B >= 1: time batched generation of B prompts")
     p.add_argument("--skinny", action="store_true", help="with --batch: skinny_gemm=True (MFMA kernels, graph up to B = 16)")
+    p.add_argument("--kv-cache", default="bf16", help="with --batch: bf16, fp8_e4m3 (generate_batch(kv_cache=...)), or a "
+                   "comma list measured alternately in this process (one JSON line per setting and round)")
+    p.add_argument("--rounds", type=int, default=1, help="with --batch: repeat the --kv-cache list this many times")
     a = p.parse_args()
+    a.kv_list = [None if k == "bf16" else k for k in a.kv_cache.split(",")]
+    if a.kv_list != [None] and a.batch < 1:
+        raise SystemExit("--kv-cache needs --batch (the single-sequence eager loop keeps a growing bf16 cache)")
     from scaling_amd.models import llama_architecture
     from scaling_amd.transformer.context.config import TransformerArchitectureConfig
     from scaling_amd.transformer.inference import (Sampler, TransformerInferenceModule, sample_argmax, sample_temperature,
@@ -88,7 +99,9 @@ def main() -> None:
     if a.batch >= 1:
         if not graph_ok:
             raise SystemExit("--batch needs a graph-safe sampler (greedy or T,K,P)")
-        batch_bench(m, a, arch, sample_fn, mode, timed, quantised)
+        for _ in range(a.rounds):
+            for kv in a.kv_list:
+                batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv)
         return
 
     m.generate(4, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn)  # warm-up (library handles, tables)
@@ -128,24 +141,31 @@ def main() -> None:
     }), flush=True)
 
 
-def batch_bench(m, a, arch, sample_fn, mode, timed, quantised) -> None:
-    """``--batch B``: per-step time of the batched decode loop (prefills and capture excluded)."""
+def batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv=None) -> None:
+    """``--batch B``: per-step time of the batched decode loop (prefills and capture excluded); ``kv``: the KV cache
+    scheme (None: bf16)."""
     from scaling_amd.ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS
 
     B, steps = a.batch, a.tokens
-    prompts = [torch.randint(1, arch.vocab_size, (max(1, a.prompt - 7 * b),)).tolist() for b in range(B)]
-    m.generate_batch(4, input_tokens=prompts, stop_tokens=[], sample_fn=sample_fn, skinny_gemm=a.skinny)  # warm-up
-    dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny)
+    if not hasattr(a, "prompts"):  # drawn once from the global stream (as ever): every setting and round decodes them
+        a.prompts = [torch.randint(1, arch.vocab_size, (max(1, a.prompt - 7 * b),)).tolist() for b in range(B)]
+    prompts = a.prompts
+    nkv = arch.attention_num_kv_heads or arch.num_attention_heads
+    hd = arch.hidden_size // arch.num_attention_heads
+    kv_bytes = arch.num_layers * 2 * nkv * (2 * hd if kv is None else hd + 4)  # K and V, all layers, one token
+    m.generate_batch(4, input_tokens=prompts, stop_tokens=[], sample_fn=sample_fn, skinny_gemm=a.skinny, kv_cache=kv)  # warm-up
+    dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv)
     te, eager = timed(lambda: dec.run([], check_every=steps + 1))
     eager_ms = 1000.0 * te / steps
     weights = sum(p.numel() * p.element_size() for p in m.parameters())
     if quantised is not None:
         weights = weights - quantised["bf16_bytes"] + quantised["fp8_bytes"]
     res = {"metric": "batched decode ms/step", "batch": B, "sampler": mode, "model": a.model, "layers": arch.num_layers,
-           "prompt": a.prompt, "tokens": steps, "weights": a.weights, "skinny_gemm": a.skinny, "eager_ms_per_step": round(eager_ms, 3),
+           "prompt": a.prompt, "tokens": steps, "weights": a.weights, "skinny_gemm": a.skinny, "kv_cache": kv or "bf16",
+           "kv_bytes_per_token": kv_bytes, "eager_ms_per_step": round(eager_ms, 3),
            "eager_tokens_per_s": round(B * 1000.0 / eager_ms, 1), "weights_gib": round(weights / 2**30, 2)}
     if B <= (SKINNY_MAX_ROWS if a.skinny else GEMV_MAX_ROWS):
-        dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny)
+        dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv)
         tc, _ = timed(dec.capture)
         tg, graph = timed(lambda: dec.run([], check_every=steps + 1))
         graph_ms = 1000.0 * tg / steps
