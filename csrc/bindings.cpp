@@ -246,6 +246,51 @@ c10::optional<at::Tensor> rope_kv_append_batch(const at::Tensor& qkv, const at::
         return c10::nullopt;
     return q;
 }
+// paged batched decode: rope_kv_append_batch over a pool of pages.  Caches [num_pages * page, nkv, hd] (FP8: codes, with
+// scales [nkv, num_pages * page]), block_table [B, max_pages] int32: sequence b's k/v go to pool row
+// block_table[b, pos[b] / page] * page + pos[b] % page.  A position outside [0, min(max_pages * page, rotary rows)) or a
+// table entry outside [0, num_pages) sets bit 0 of err, writes nothing and zeroes that sequence's q.  Rotation, FP8
+// quantisation and q are the slab kernel's code.
+c10::optional<at::Tensor> rope_kv_append_paged(const at::Tensor& qkv, const at::Tensor& cosb, const at::Tensor& sinb,
+                                               const at::Tensor& pos, int64_t nq, int64_t nkv, int64_t rot_dim,
+                                               bool interleaved, at::Tensor kc, at::Tensor vc, at::Tensor err,
+                                               const at::Tensor& block_table, int64_t page,
+                                               const c10::optional<at::Tensor>& k_scale,
+                                               const c10::optional<at::Tensor>& v_scale) {
+    TORCH_CHECK(err_word(err), "rope_kv_append_paged: err must be an int32 GPU tensor");
+    check_cuda(qkv, "qkv");
+    TORCH_CHECK(qkv.dim() == 3, "rope_kv_append_paged: qkv must be [B, nq + 2 nkv, hd]");
+    TORCH_CHECK(page > 0 && page % 32 == 0, "rope_kv_append_paged: the page size must be a positive multiple of 32");
+    const int64_t B = qkv.size(0), hd = qkv.size(-1);
+    TORCH_CHECK(kc.dim() == 3 && kc.size(0) > 0 && kc.size(0) % page == 0 && kc.size(0) < (int64_t)1 << 31 &&
+                    vc.sizes() == kc.sizes() && pos.numel() == B,
+                "rope_kv_append_paged: caches must hold a whole number of pages and pos one entry per sequence");
+    TORCH_CHECK(block_table.is_cuda() && block_table.scalar_type() == at::kInt && block_table.dim() == 2 &&
+                    block_table.size(0) == B && block_table.size(1) >= 1 && block_table.stride(1) == 1,
+                "rope_kv_append_paged: block_table must be an int32 GPU tensor [B, max_pages] with unit last stride");
+    const bool q8 = k_scale.has_value() || v_scale.has_value();
+    if (q8 && !kv_scales_ok("rope_kv_append_paged", qkv, kc, vc, k_scale, v_scale, nkv)) return c10::nullopt;
+    const auto cdt = q8 ? kc.scalar_type() : qkv.scalar_type();
+    if (!(B >= 1 && qkv.is_contiguous() && qkv.size(1) == nq + 2 * nkv && kc.is_contiguous() && vc.is_contiguous() &&
+          kc.size(1) == nkv && kc.size(2) == hd && kc.scalar_type() == cdt &&
+          vc.scalar_type() == cdt && kc.is_cuda() && vc.is_cuda() && pos.is_cuda() &&
+          pos.scalar_type() == at::kLong && pos.is_contiguous() && cosb.is_cuda() && sinb.is_cuda() &&
+          cosb.scalar_type() == at::kFloat && sinb.scalar_type() == at::kFloat && cosb.is_contiguous() &&
+          sinb.is_contiguous() && cosb.size(-1) == rot_dim / 2 && sinb.sizes() == cosb.sizes() && rot_dim <= hd &&
+          (uintptr_t)qkv.data_ptr() % 16 == 0 && (uintptr_t)kc.data_ptr() % 16 == 0 && (uintptr_t)vc.data_ptr() % 16 == 0))
+        return c10::nullopt;
+    const at::DeviceGuard g(qkv.device());
+    auto q = at::empty({B, nq, hd}, qkv.options());
+    const AppendPages pg{block_table.data_ptr<int>(), block_table.stride(0), (int)page, (int)(kc.size(0) / page)};
+    if (!sa_launch::rope_kv_append(dt(qkv), interleaved, qkv.data_ptr(), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                                   pos.data_ptr<int64_t>(), cosb.data_ptr<float>(), sinb.data_ptr<float>(), (int)nq,
+                                   (int)nkv, (int)hd, (int)rot_dim,
+                                   std::min<int64_t>(block_table.size(1) * page, cosb.size(0)), err.data_ptr<int>(),
+                                   cur_stream(), (int)B, 0, q8 ? k_scale->data_ptr<float>() : nullptr,
+                                   q8 ? v_scale->data_ptr<float>() : nullptr, q8 ? k_scale->stride(0) : 0, &pg))
+        return c10::nullopt;
+    return q;
+}
 
 // ------------------------------------------------------------------ cross entropy
 std::vector<at::Tensor> xent_stats(const at::Tensor& logits, const at::Tensor& target, int64_t v0) {
@@ -655,11 +700,14 @@ std::vector<at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const a
                                const at::Tensor& cu_k, int64_t max_q, double scale, bool causal, int64_t window,
                                double p_drop, int64_t seed, int64_t local_heads, int64_t max_k,
                                const c10::optional<at::Tensor>& k_range, const c10::optional<at::Tensor>& k_scale,
-                               const c10::optional<at::Tensor>& v_scale) {
+                               const c10::optional<at::Tensor>& v_scale, const c10::optional<at::Tensor>& block_table,
+                               int64_t page_size) {
     // k_range: int32 [nseg, 2] = (first key row, key count) per segment, replacing cu_k (decode kernel only): the
     // keys of a static batched cache sit in one fixed-capacity slab per sequence, not packed back to back
     // k_scale / v_scale: FP8 K/V (decode kernel only, bf16 q): k / v hold e4m3fn codes (uint8 or float8_e4m3fn) and the
     // scales are fp32 [Hkv, key rows], one power of two per (kv head, row)
+    // block_table int32 [nseg, max_pages] + page_size (with k_range = (0, length); decode kernel only): k / v (and the
+    // scales) are a pool of pages of page_size rows, key j of segment s is row block_table[s, j / page] * page + j % page
     const bool q8 = k_scale.has_value() || v_scale.has_value();
     check_qkv(q, "q");
     if (q8) {
@@ -709,6 +757,16 @@ std::vector<at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const a
                     "no dropout)");
         TORCH_CHECK(v.size(0) == k.size(0), "flash_attn: k and v must hold the same number of rows");
     }
+    if (block_table.has_value()) {
+        TORCH_CHECK(k_range.has_value(), "flash_attn: block_table needs k_range (start 0, length per segment)");
+        TORCH_CHECK(page_size > 0 && page_size % 32 == 0, "flash_attn: page_size must be a positive multiple of 32");
+        TORCH_CHECK(block_table->is_cuda() && block_table->scalar_type() == at::kInt && block_table->dim() == 2 &&
+                    block_table->size(0) == a.nseg && block_table->size(1) >= 1 && block_table->stride(1) == 1,
+                    "flash_attn: block_table must be an int32 GPU tensor [nseg, max_pages] with unit last stride");
+        TORCH_CHECK(k.size(0) > 0 && k.size(0) % page_size == 0 && k.size(0) < (int64_t)1 << 31 &&
+                    block_table->size(1) * page_size < (int64_t)1 << 31,
+                    "flash_attn: with block_table, k / v must hold a whole number of pages (fewer than 2^31 rows)");
+    }
     if (q8)
         TORCH_CHECK(p_drop == 0.0 && max_q * grp <= 32,
                     "flash_attn: FP8 k / v are supported by the decode kernel only (max_q * heads per kv head <= 32, "
@@ -722,6 +780,10 @@ std::vector<at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const a
         if (q8) { d.k_scale = k_scale->data_ptr<float>(); d.v_scale = v_scale->data_ptr<float>(); d.s_head = k_scale->stride(0); }
         d.k_range = k_range.has_value() ? k_range->data_ptr<int>() : nullptr; d.k_rows = k.size(0); d.Hq = a.Hq; d.Hkv = a.Hkv; d.causal = a.causal;
         d.window = a.window; d.local_heads = a.local_heads; d.scale_log2 = a.scale_log2; d.Tq = T;
+        if (block_table.has_value()) {
+            d.block_table = block_table->data_ptr<int>(); d.bt_stride = block_table->stride(0); d.page = (int)page_size;
+            d.num_pages = (int)(k.size(0) / page_size); d.max_pages = (int)block_table->size(1);
+        }
         sa_launch::fa_decode_plan(max_k > 0 ? max_k : k.size(0), a.Hkv, a.nseg, d.split_keys, d.nsplit);
         auto part_o = at::empty({(int64_t)d.nsplit, T, H, D}, q.options().dtype(at::kFloat));
         auto part_ml = at::empty({(int64_t)d.nsplit, T, H, 2}, q.options().dtype(at::kFloat));
@@ -1028,6 +1090,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rope_kv_append_batch", &rope_kv_append_batch, "batched graph decode: rope_kv_append for one token of each of B sequences, one launch",
           py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("nq"), py::arg("nkv"), py::arg("rot_dim"), py::arg("interleaved"),
           py::arg("kc"), py::arg("vc"), py::arg("err"), py::arg("cap"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+    m.def("rope_kv_append_paged", &rope_kv_append_paged, "paged batched decode: rope_kv_append_batch into the pages a block table names, one launch",
+          py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("nq"), py::arg("nkv"), py::arg("rot_dim"), py::arg("interleaved"),
+          py::arg("kc"), py::arg("vc"), py::arg("err"), py::arg("block_table"), py::arg("page"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
     m.def("xent_stats", &xent_stats, "cross-entropy row statistics");
     m.def("xent_bwd", &xent_bwd, "cross-entropy backward");
     m.def("embed_fwd", &embed_fwd, "vocab-parallel embedding forward");
@@ -1049,6 +1114,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("xgmi_emulate", &xgmi_emulate, "per-rank proxy: emulated collective (HBM traffic on nwg CUs, held to us)",
           py::arg("src"), py::arg("scratch"), py::arg("bytes"), py::arg("us"), py::arg("nwg") = 16);
     m.def("dropout_add", &dropout_add, "residual + dropout(x) with a hashed keep mask", py::arg("x"), py::arg("res"), py::arg("p"), py::arg("seed"));
-    m.def("fa_fwd", &fa_fwd, "flash attention forward (bf16/fp16, optional attention dropout)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("max_k") = -1, py::arg("k_range") = py::none(), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+    m.def("fa_fwd", &fa_fwd, "flash attention forward (bf16/fp16, optional attention dropout)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("max_k") = -1, py::arg("k_range") = py::none(), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("page_size") = 0);
     m.def("fa_bwd", &fa_bwd, "flash attention backward (optional strided dq/dk/dv outputs)", py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("max_k"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(), py::arg("dv_out") = py::none(), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("rope_cos") = py::none(), py::arg("rope_sin") = py::none(), py::arg("rope_pos") = py::none(), py::arg("rope_dim") = 0, py::arg("rope_seq") = 1, py::arg("rope_interleaved") = false);
 }

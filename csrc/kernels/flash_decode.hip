@@ -27,7 +27,17 @@
 //    would be equal only short of underflow of P; the image form has no such condition and was kept.)
 // o and lse are bit for bit those of the bf16 kernel on the dequantised cache.  Rows past k_end load neither codes nor
 // scales.
+//
+// Paged K/V (template flag PG; DecArgs::block_table): k / v are a pool of pages of `page` rows, page % 32 == 0, and
+// logical key j of segment s is pool row block_table[s][j / page] * page + j % page (k_range gives (0, length)).  Splits
+// start at multiples of 32, so every 32-key tile lies in one page and needs ONE wave-uniform table entry, which replaces
+// the tile's base row; everything else -- tiles, split plan, masking, partials, the FP8 loads -- is the slab form, so o
+// and lse are bit for bit those of the k_range call on a contiguous buffer holding the same rows.  The entry of a tile is
+// fetched one tile before the tile's loads are issued (two tiles earlier than that in the FP8 form, which loads two
+// tiles ahead), never for a tile at or past k_end, and an entry outside [0, num_pages) is not dereferenced: its keys are
+// masked.  The slab instantiations (PG = false) contain none of this.
 #include <algorithm>
+#include <type_traits>
 
 #include "flash_attn.h"
 #include "launch.h"
@@ -84,7 +94,7 @@ __device__ __forceinline__ void merge_dim(const DecArgs& a, int64_t tok, int hq,
     if (d == 0) a.lse[(int64_t)hq * a.lse_stride + tok] = L > 0.f ? (M + __log2f(L)) * 0.69314718055994530942f : INFINITY;
 }
 
-template <int D, bool F16, bool Q8>
+template <int D, bool F16, bool Q8, bool PG>
 __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
     static_assert(!(F16 && Q8), "FP8 K/V: bf16 queries only");
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -94,7 +104,11 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
     const int q0s = a.cu_q[seg];
     const int Lq = a.cu_q[seg + 1] - q0s;
     int k0s, Lk;
-    if (a.k_range) {  // (first row, count) of this segment's keys, clipped to the buffer
+    if constexpr (PG) {  // (0, length): the keys are the table's pages in order, clipped to the table's width
+        k0s = 0;
+        Lk = a.k_range[2 * seg + 1];
+        Lk = (int)min((int64_t)max(Lk, 0), (int64_t)a.max_pages * a.page);
+    } else if (a.k_range) {  // (first row, count) of this segment's keys, clipped to the buffer
         k0s = a.k_range[2 * seg];
         Lk = a.k_range[2 * seg + 1];
         if (k0s < 0 || Lk < 0 || k0s > a.k_rows) k0s = 0, Lk = 0;
@@ -136,6 +150,23 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
     const float* ksb = Q8 ? a.k_scale + (int64_t)hk * a.s_head + k0s : nullptr;
     const float* vsb = Q8 ? a.v_scale + (int64_t)hk * a.s_head + k0s : nullptr;
 
+    // paged: the pool row of a tile's first key (the tile's base row), -1 for a table entry outside the pool; tiles are
+    // asked for in order from k_begin, one call per tile.  slab: the base row of tile kt is kt itself (row_t stays int)
+    using row_t = std::conditional_t<PG, int64_t, int>;
+    const int* bt = PG ? a.block_table + (int64_t)seg * a.bt_stride : nullptr;
+    int c_kt = k_begin, c_pg = PG ? k_begin / a.page : 0, c_in = PG ? k_begin % a.page : 0;
+    auto next_base = [&]() -> int64_t {
+        int64_t base = -1;
+        if (c_kt < k_end) {  // k_end <= max_pages * page: c_pg is inside the table
+            const int e = bt[c_pg];
+            if ((unsigned)e < (unsigned)a.num_pages) base = (int64_t)e * a.page + c_in;
+        }
+        c_kt += 32;
+        c_in += 32;
+        if (c_in >= a.page) c_in = 0, ++c_pg;
+        return base;
+    };
+
     // FP8: the codes and scales of a tile are loaded two tiles ahead (n1, n2).  A tile of codes is half the bytes of a
     // bf16 tile and a workgroup is one wave, so two tiles in flight are the bf16 form's bytes in flight, and their round
     // trip overlaps the decode -> MFMA -> softmax -> MFMA chain of the tile being computed.  The loads are unconditional
@@ -148,40 +179,55 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
         u32x4 vq[QP];
         float vs[QP];
     };
-    auto load_q8 = [&](int kt, Q8Tile& t) {  // rows past k_end load neither codes nor scales
-        const bool krow = kt + r < k_end;
-        const uint8_t* kp = kb8 + (int64_t)(krow ? kt + r : kt) * a.k_tok;
+    auto load_q8 = [&](int kt, int64_t tb, Q8Tile& t) {  // rows past k_end load neither codes nor scales
+        const bool tile_on = !PG || tb >= 0;
+        const row_t ab = PG ? (row_t)tb : (row_t)kt;  // address of key kt + i: row ab + i
+        const bool krow = kt + r < k_end && tile_on;
+        const uint8_t* kp = kb8 + (int64_t)(krow ? ab + r : (PG ? 0 : kt)) * a.k_tok;
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks)
             t.kq[ks] = krow ? *reinterpret_cast<const u32x2*>(kp + 16 * ks + 8 * h) : u32x2{0, 0};
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int kg = kt + 8 * g + 4 * h;
-            if (kg + 3 < k_end) {  // one 16-byte load; a slab may start at any row, so only dword alignment is assumed
-                t.ksc[g] = *reinterpret_cast<const f32x4_a4*>(ksb + kg);
+            const row_t ag = ab + 8 * g + 4 * h;
+            if (kg + 3 < k_end && tile_on) {  // one 16-byte load; a slab may start at any row, so only dword alignment is assumed
+                t.ksc[g] = *reinterpret_cast<const f32x4_a4*>(ksb + ag);
             } else {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) t.ksc[g][i] = kg + i < k_end ? ksb[kg + i] : 0.f;
+                for (int i = 0; i < 4; ++i) t.ksc[g][i] = kg + i < k_end && tile_on ? ksb[ag + i] : 0.f;
             }
         }
 #pragma unroll
         for (int p = 0; p < QP; ++p) {
             const int id = lane + 64 * p, row = id / (D / 16), c = id % (D / 16);
-            const bool on = kt + row < k_end;
-            t.vq[p] = on ? *reinterpret_cast<const u32x4*>(vb8 + (int64_t)(kt + row) * a.v_tok + c * 16) : u32x4{0, 0, 0, 0};
-            t.vs[p] = on ? vsb[kt + row] : 0.f;
+            const bool on = kt + row < k_end && tile_on;
+            t.vq[p] = on ? *reinterpret_cast<const u32x4*>(vb8 + (int64_t)(ab + row) * a.v_tok + c * 16) : u32x4{0, 0, 0, 0};
+            t.vs[p] = on ? vsb[ab + row] : 0.f;
         }
     };
     Q8Tile n1, n2;
+    // tb_cur: base row of the tile being computed; tb_nxt: of the next tile whose loads are issued (bf16: kt + 32, FP8:
+    // kt + 64), fetched an iteration before it is needed so that no load of a tile waits for its table entry
+    int64_t tb_cur = -1, tb_nxt = -1;
+    bool on_n1 = true, on_n2 = true;  // FP8 paged: whether the tiles in n1 / n2 have a table entry inside the pool
     if constexpr (Q8) {
-        load_q8(k_begin, n1);
-        load_q8(k_begin + 32, n2);
+        const int64_t b0 = PG ? next_base() : 0, b1 = PG ? next_base() : 0;
+        if constexpr (PG) tb_nxt = next_base(), on_n1 = b0 >= 0, on_n2 = b1 >= 0;
+        load_q8(k_begin, b0, n1);
+        load_q8(k_begin + 32, b1, n2);
+    } else if constexpr (PG) {
+        tb_cur = next_base();
+        tb_nxt = next_base();
     }
 
     for (int kt = k_begin; kt < k_end; kt += 32) {
         // K rows (A operand: key kt + r, dims 16 ks + 8 h) and the V tile are all issued before anything waits on
         // them: one memory round trip per tile instead of V, then K
-        const bool krow = kt + r < k_end;
+        bool tile_on = true;  // paged: whether this tile's table entry lies inside the pool
+        if constexpr (PG && !Q8) tile_on = tb_cur >= 0;
+        const row_t ab = PG ? (row_t)tb_cur : (row_t)kt;  // bf16 form: address of key kt + i is row ab + i
+        const bool krow = kt + r < k_end && tile_on;
         u16x8 kv[NKS];
         // PASSES 16-byte loads per lane of 8 bf16 each
         constexpr int PASSES = Q8 ? 1 : 32 * D / 8 / 64;
@@ -190,7 +236,11 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
         if constexpr (Q8) {
             cur = n1;
             n1 = n2;
-            load_q8(kt + 64, n2);
+            load_q8(kt + 64, tb_nxt, n2);
+            if constexpr (PG) {
+                tile_on = on_n1, on_n1 = on_n2, on_n2 = tb_nxt >= 0;
+                tb_nxt = next_base();  // tile kt + 96: loaded by the next iteration
+            }
             // codes -> bf16 in registers (exact); the key's scale multiplies its fp32 score below
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks) {
@@ -205,7 +255,7 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
                 kv[ks] = __builtin_bit_cast(u16x8, w);
             }
         } else {
-            const u16* kp = kb + (int64_t)(krow ? kt + r : kt) * a.k_tok;
+            const u16* kp = kb + (int64_t)(krow ? ab + r : (PG ? 0 : kt)) * a.k_tok;
 #pragma unroll
             for (int ks = 0; ks < NKS; ++ks)
                 kv[ks] = krow ? *reinterpret_cast<const u16x8*>(kp + 16 * ks + 8 * h) : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
@@ -213,8 +263,13 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
 #pragma unroll
             for (int p = 0; p < PASSES; ++p) {
                 const int id = lane + 64 * p, row = id / (D / 8), c = id % (D / 8);
-                vv[p] = kt + row < k_end ? *reinterpret_cast<const u16x8*>(vb + (int64_t)(kt + row) * a.v_tok + c * 8)
-                                         : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                vv[p] = kt + row < k_end && tile_on
+                            ? *reinterpret_cast<const u16x8*>(vb + (int64_t)(ab + row) * a.v_tok + c * 8)
+                            : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            }
+            if constexpr (PG) {  // the next tile's entry is in hand; fetch the one after it
+                tb_cur = tb_nxt;
+                tb_nxt = next_base();
             }
         }
         // S^T = K Q^T
@@ -254,6 +309,7 @@ __global__ __launch_bounds__(64) void fa_decode_kernel(DecArgs a) {
         for (int j = 0; j < 16; ++j) {
             const int key = kt + crow(j) + 4 * h;
             bool ok = valid && key < k_end;
+            if constexpr (PG) ok = ok && tile_on;
             if (a.causal) ok = ok && key <= qi + off;
             if (win >= 0) ok = ok && key >= qi + off - win && (a.causal || key <= qi + off + win);
             float x;
@@ -312,11 +368,14 @@ template <int D, bool F16>
 void launch(const DecArgs& a, int nseg, hipStream_t st) {
     const dim3 grid(a.nsplit, a.Hkv, nseg);
     bool q8 = false;
+    const bool pg = a.block_table != nullptr;
     if constexpr (!F16) {
         q8 = a.k_scale != nullptr;
-        if (q8) hipLaunchKernelGGL((fa_decode_kernel<D, false, true>), grid, dim3(64), 0, st, a);
+        if (q8 && pg) hipLaunchKernelGGL((fa_decode_kernel<D, false, true, true>), grid, dim3(64), 0, st, a);
+        else if (q8) hipLaunchKernelGGL((fa_decode_kernel<D, false, true, false>), grid, dim3(64), 0, st, a);
     }
-    if (!q8) hipLaunchKernelGGL((fa_decode_kernel<D, F16, false>), grid, dim3(64), 0, st, a);
+    if (!q8 && pg) hipLaunchKernelGGL((fa_decode_kernel<D, F16, false, true>), grid, dim3(64), 0, st, a);
+    else if (!q8) hipLaunchKernelGGL((fa_decode_kernel<D, F16, false, false>), grid, dim3(64), 0, st, a);
     hipLaunchKernelGGL((fa_decode_combine_kernel<D, F16>), dim3((unsigned)a.Tq, a.Hq), dim3(D), 0, st, a);
 }
 

@@ -17,6 +17,9 @@ void norm_bwd(int dtype, bool layer, const void* dy, const void* x, const void* 
               const void* dadd = nullptr);
 }  // namespace sa_launch
 
+// paged K/V cache, append side: the block table [B][stride] int32 of page ids, the page size in rows and the pool's pages
+struct AppendPages { const int* table; int64_t stride; int page, num_pages; };
+
 namespace sa_launch {
 // swiglu_rope.hip
 void swiglu_fwd(int dtype, const void* a, const void* b, int64_t lda, void* out, int64_t rows, int F, hipStream_t st);
@@ -34,10 +37,13 @@ void rope(int dtype, bool interleaved, const void* x, int64_t x_tok, int64_t x_h
 // row and the v row are quantised per row exactly as ops/quant.py quantize_rows_fp8 does.  q_out is bitwise the bf16
 // form's.  A k / v value that is NaN is stored as 0, one above 2^127 (infinity included) as +-2^127; bit 1 of *err is
 // then set (bit 0: the position error)
+// pages != nullptr: the paged cache.  kc / vc (and the scales) are a pool of num_pages pages of `page` rows and
+// sequence b writes row table[b * stride + pos[b] / page] * page + pos[b] % page (cap is unused; lim = min(table width
+// * page, rotary table rows)); an entry outside [0, num_pages) counts as a position error
 bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, void* kc, void* vc, const int64_t* pos,
                     const float* cosb, const float* sinb, int nq, int nkv, int hd, int rd, int64_t lim, int* err,
                     hipStream_t st, int B = 1, int64_t cap = 0, float* k_scale = nullptr, float* v_scale = nullptr,
-                    int64_t s_head = 0);
+                    int64_t s_head = 0, const AppendPages* pages = nullptr);
 }  // namespace sa_launch
 
 namespace sa_launch {
@@ -104,6 +110,11 @@ struct DecArgs {
     float* part_ml;  // [nsplit][Tq][Hq][2] running max (log2 units) and sum
     uint16_t* o; int64_t o_tok, o_head;
     float* lse; int64_t lse_stride;
+    // paged K/V (block_table != nullptr, with k_range = (0, length) per segment): k / v (and the FP8 scales) are a pool
+    // of num_pages pages of `page` rows (page % 32 == 0: a 32-key tile lies in one page); logical key j of segment s is
+    // pool row block_table[s * bt_stride + j / page] * page + j % page.  max_pages = the table's width; an entry
+    // outside [0, num_pages) is never dereferenced (its keys are masked), entries past a segment's length never read
+    const int* block_table; int64_t bt_stride; int page, num_pages, max_pages;
 };
 namespace sa_launch {
 void fa_decode_plan(int64_t max_k, int Hkv, int nseg, int& split_keys, int& nsplit);

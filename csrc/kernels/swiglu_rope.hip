@@ -202,12 +202,22 @@ __device__ __forceinline__ void append_chunk(const T* xr, int c, int rc, int hal
     }
 }
 
-template <typename T, bool IL>
+// Paged form (template flag PG; AppendPages): the caches are a pool of pages and sequence b's row is
+// table[b][pos / page] * page + pos % page; lim = min(table width * page, rotary table rows).  A table entry outside
+// [0, num_pages) is a position error like a position outside [0, lim): nothing is written, q is zeroed, bit 0 of *err.
+// Rotation, quantisation and q_out are the slab form's code.  The paged kernels are the instantiations with one trailing
+// AppendPages argument (the pack P); with the empty pack the kernels keep the slab form's signature and code.
+template <typename A>
+__device__ __forceinline__ const A& only_arg(const A& a) { return a; }
+
+template <typename T, bool IL, typename... P>
 __global__ __launch_bounds__(256) void rope_kv_append_kernel(const T* __restrict__ x, T* __restrict__ q_out,
                                                              T* __restrict__ kc, T* __restrict__ vc,
                                                              const int64_t* __restrict__ pos, const float* cosb,
                                                              const float* sinb, int nq, int nkv, int hd, int rd,
-                                                             int64_t lim, int64_t cap, int* __restrict__ err) {
+                                                             int64_t lim, int64_t cap, int* __restrict__ err,
+                                                             P... pages) {
+    constexpr bool PG = sizeof...(P) == 1;
     const int half = rd / 2;
     const int rc = IL ? rd / 8 : half / 8;
     const int CR = rc + (hd - rd) / 8;
@@ -216,7 +226,22 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(const T* __restrict
     const int64_t ps = pos[b];
     x += (int64_t)b * nh * hd;
     q_out += (int64_t)b * nq * hd;
-    if (ps < 0 || ps >= lim) {
+    bool bad = false;
+    int64_t prow = 0;  // paged: the pool row
+    if constexpr (PG) {
+        const AppendPages& pg = only_arg(pages...);
+        bad = ps < 0 || ps >= lim;
+        if (!bad) {
+            const int e = pg.table[b * pg.stride + ps / pg.page];
+            bad = (unsigned)e >= (unsigned)pg.num_pages;
+            prow = (int64_t)e * pg.page + ps % pg.page;
+        }
+    }
+    auto cache_row = [&]() -> int64_t {
+        if constexpr (PG) return prow;
+        else return b * cap + ps;
+    };
+    if (PG ? bad : (ps < 0 || ps >= lim)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) *err = 1;
         for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nq * hd / 8; i += gridDim.x * blockDim.x) {
             const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -230,8 +255,8 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(const T* __restrict
         const T* xr = x + (int64_t)h * hd;
         T* orow;
         if (h < nq) orow = q_out + (int64_t)h * hd;
-        else if (h < nq + nkv) orow = kc + ((b * cap + ps) * nkv + (h - nq)) * hd;
-        else orow = vc + ((b * cap + ps) * nkv + (h - nq - nkv)) * hd;
+        else if (h < nq + nkv) orow = kc + (cache_row() * nkv + (h - nq)) * hd;
+        else orow = vc + (cache_row() * nkv + (h - nq - nkv)) * hd;
         if (h >= nq + nkv) {  // v: plain copy of the row's chunks
             for (int e = 8 * c; e < hd; e += 8 * CR) {
                 float v[8];
@@ -279,15 +304,16 @@ __device__ __forceinline__ uint2 e4m3_pack8(const float (&v)[8], float inv) {
 // when amax's significand is <= 1.75); codes = e4m3(value / s), |value / s| <= 448 by construction.  The remaining
 // waves rotate the q heads, one lane per chunk as the bf16 kernel (q_out is bitwise its output).  A non-finite k / v
 // value never becomes the NaN code: kv_finite_bf replaces it and bit 1 of *err is set; bit 0 is the position error.
-template <bool IL>
+template <bool IL, typename... P>
 __global__ __launch_bounds__(256) void rope_kv_append_q8_kernel(const u16* __restrict__ x, u16* __restrict__ q_out,
                                                                 uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
                                                                 float* __restrict__ k_scale, float* __restrict__ v_scale,
                                                                 int64_t s_head, const int64_t* __restrict__ pos,
                                                                 const float* cosb, const float* sinb, int nq, int nkv,
                                                                 int hd, int rd, int64_t lim, int64_t cap,
-                                                                int* __restrict__ err) {
+                                                                int* __restrict__ err, P... pages) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool PG = sizeof...(P) == 1;
     const int half = rd / 2;
     const int rc = IL ? rd / 8 : half / 8;
     const int CR = rc + (hd - rd) / 8;
@@ -296,7 +322,18 @@ __global__ __launch_bounds__(256) void rope_kv_append_q8_kernel(const u16* __res
     const int64_t ps = pos[b];
     x += (int64_t)b * nh * hd;
     q_out += (int64_t)b * nq * hd;
-    if (ps < 0 || ps >= lim) {
+    bool oob = false;
+    int64_t prow = 0;  // paged: the pool row
+    if constexpr (PG) {
+        const AppendPages& pg = only_arg(pages...);
+        oob = ps < 0 || ps >= lim;
+        if (!oob) {
+            const int e = pg.table[b * pg.stride + ps / pg.page];
+            oob = (unsigned)e >= (unsigned)pg.num_pages;
+            prow = (int64_t)e * pg.page + ps % pg.page;
+        }
+    }
+    if (PG ? oob : (ps < 0 || ps >= lim)) {
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(err, 1);
         for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nq * hd / 8; i += gridDim.x * blockDim.x) {
             const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -348,7 +385,7 @@ __global__ __launch_bounds__(256) void rope_kv_append_q8_kernel(const u16* __res
     if (es < -100) es = -100;  // covers the subnormal amax (E == 0)
     const float s = bits == 0u ? 1.f : __uint_as_float((uint32_t)(es + 127) << 23);
     const float inv = bits == 0u ? 1.f : __uint_as_float((uint32_t)(127 - es) << 23);
-    const int64_t row = (int64_t)b * cap + ps;
+    const int64_t row = PG ? prow : (int64_t)b * cap + ps;
     uint8_t* orow = (isv ? vc : kc) + (row * nkv + hk) * hd;
     if (e0 >= 0) *reinterpret_cast<uint2*>(orow + e0) = e4m3_pack8(o0, inv);
     if (e1 >= 0) *reinterpret_cast<uint2*>(orow + e1) = e4m3_pack8(o1, inv);
@@ -365,7 +402,10 @@ static int grid_for(int64_t n) {
 namespace sa_launch {
 bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, void* kc, void* vc, const int64_t* pos,
                     const float* cosb, const float* sinb, int nq, int nkv, int hd, int rd, int64_t lim, int* err,
-                    hipStream_t st, int B, int64_t cap, float* k_scale, float* v_scale, int64_t s_head) {
+                    hipStream_t st, int B, int64_t cap, float* k_scale, float* v_scale, int64_t s_head,
+                    const AppendPages* pages) {
+    const AppendPages pg = pages != nullptr ? *pages : AppendPages{nullptr, 0, 0, 0};
+    if (pages != nullptr && (pg.table == nullptr || pg.page < 1 || pg.num_pages < 1)) return false;
     if (dtype == DT_F32 || hd % 8 || (interleaved ? rd % 8 : rd % 16) || B < 1 || B > 65535) return false;
     const int CR = (interleaved ? rd / 8 : rd / 16) + (hd - rd) / 8;
     if (k_scale != nullptr) {  // FP8 cache: one wave per k / v head, then the q chunks
@@ -374,7 +414,13 @@ bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, voi
 #define SA_RKV8(IL)                                                                                                 \
     hipLaunchKernelGGL((rope_kv_append_q8_kernel<IL>), g, 256, 0, st, (const u16*)x, (u16*)q_out, (uint8_t*)kc,      \
                        (uint8_t*)vc, k_scale, v_scale, s_head, pos, cosb, sinb, nq, nkv, hd, rd, lim, cap, err)
-        if (interleaved) SA_RKV8(true); else SA_RKV8(false);
+#define SA_RKV8P(IL)                                                                                                  \
+    hipLaunchKernelGGL((rope_kv_append_q8_kernel<IL, AppendPages>), g, 256, 0, st, (const u16*)x, (u16*)q_out,        \
+                       (uint8_t*)kc, (uint8_t*)vc, k_scale, v_scale, s_head, pos, cosb, sinb, nq, nkv, hd, rd, lim,   \
+                       cap, err, pg)
+        if (pages != nullptr) { if (interleaved) SA_RKV8P(true); else SA_RKV8P(false); }
+        else { if (interleaved) SA_RKV8(true); else SA_RKV8(false); }
+#undef SA_RKV8P
 #undef SA_RKV8
         return true;
     }
@@ -382,8 +428,17 @@ bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, voi
 #define SA_RKV(TT, IL)                                                                                            \
     hipLaunchKernelGGL((rope_kv_append_kernel<TT, IL>), g, 256, 0, st, (const TT*)x, (TT*)q_out, (TT*)kc, (TT*)vc, \
                        pos, cosb, sinb, nq, nkv, hd, rd, lim, cap, err)
-    if (dtype == DT_BF16) { if (interleaved) SA_RKV(u16, true); else SA_RKV(u16, false); }
-    else { if (interleaved) SA_RKV(f16, true); else SA_RKV(f16, false); }
+#define SA_RKVP(TT, IL)                                                                                            \
+    hipLaunchKernelGGL((rope_kv_append_kernel<TT, IL, AppendPages>), g, 256, 0, st, (const TT*)x, (TT*)q_out,      \
+                       (TT*)kc, (TT*)vc, pos, cosb, sinb, nq, nkv, hd, rd, lim, cap, err, pg)
+    if (pages != nullptr) {
+        if (dtype == DT_BF16) { if (interleaved) SA_RKVP(u16, true); else SA_RKVP(u16, false); }
+        else { if (interleaved) SA_RKVP(f16, true); else SA_RKVP(f16, false); }
+    } else {
+        if (dtype == DT_BF16) { if (interleaved) SA_RKV(u16, true); else SA_RKV(u16, false); }
+        else { if (interleaved) SA_RKV(f16, true); else SA_RKV(f16, false); }
+    }
+#undef SA_RKVP
 #undef SA_RKV
     return true;
 }

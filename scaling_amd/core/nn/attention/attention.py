@@ -449,8 +449,226 @@ class BatchStaticKVCacheFP8(_FP8Rows, BatchStaticKVCache):
         return self.k, self.v, st.k_range
 
 
+PAGE_MULTIPLE = 32  # the decode kernel's key tile: a page is a whole number of tiles, so no tile straddles two pages
+
+
+def check_page_size(page_size: int, who: str) -> int:
+    if not isinstance(page_size, int) or isinstance(page_size, bool) or page_size <= 0 or page_size % PAGE_MULTIPLE:
+        raise ValueError(f"{who}: page_size must be a positive multiple of {PAGE_MULTIPLE} (the decode kernel's key "
+                         f"tile), got {page_size!r}")
+    return page_size
+
+
+class PageAllocator:
+    """Host-side free list of the page ids of a paged KV pool, one allocator for all layers (a page id names the same
+    page in every layer's pool).  Pages ``[0, reserved)`` are never handed out: they are the rows' parking pages."""
+
+    def __init__(self, num_pages: int, reserved: int = 0) -> None:
+        if num_pages <= reserved:
+            raise ValueError(f"paged KV cache: a pool of {num_pages} pages leaves none beside the {reserved} parking pages")
+        self.num_pages, self.reserved = num_pages, reserved
+        self._free = list(range(num_pages - 1, reserved - 1, -1))  # popped from the end: lowest id first
+        self.peak_in_use = 0
+
+    @property
+    def free_pages(self) -> int:
+        return len(self._free)
+
+    @property
+    def in_use(self) -> int:
+        return self.num_pages - self.reserved - len(self._free)
+
+    def alloc(self, n: int) -> list[int]:
+        """``n`` pages; ``RuntimeError`` naming the pool size when fewer are free (nothing is taken then)."""
+        if n > len(self._free):
+            raise RuntimeError(f"paged KV cache: out of pages ({n} wanted, {len(self._free)} free; the pool holds "
+                               f"{self.num_pages} pages of which {self.reserved} are parking pages)")
+        out = [self._free.pop() for _ in range(n)]
+        self.peak_in_use = max(self.peak_in_use, self.in_use)
+        return out
+
+    def free(self, pages: Sequence[int]) -> None:
+        for p in pages:
+            assert self.reserved <= p < self.num_pages and p not in self._free, f"page {p} is not allocated"
+        self._free.extend(reversed(list(pages)))
+
+
+class PagedDecodeState(BatchDecodeState):
+    """``BatchDecodeState`` of a paged KV cache, shared by every layer's ``PagedKVCache``; every tensor keeps its address
+    for the life of the decoder, so a captured step sees admissions and page allocations as changed device values.
+
+    * ``pos`` [B] int64: the position of the token row b feeds;
+    * ``k_range`` [B, 2] int32 = (0, pos[b] + 1): the existing key-range layout with start 0, length in column 1;
+    * ``block_table`` [B, max_pages] int32: logical key j of row b is pool row ``block_table[b, j // page] * page +
+      j % page``; entries of pages a row does not own are -1, which the kernels never dereference;
+    * ``live`` [B] int64, 1 for a row that holds a request: ``advance`` moves live rows only;
+    * ``err`` the shared error word.
+
+    Parking: page b of the pool belongs to row b for good.  A row without a request sits at ``pos = 0``, length 1, with
+    ``block_table[b] = [b, -1, ...]``: each step it writes row 0 of its own parking page and reads that one (finite) key,
+    so no idle row writes where a live row reads, no two rows write one address, and the sampler sees finite logits.
+    ``capacity`` = ``max_pages * page`` sizes the split plan, as the slab capacity does."""
+
+    def __init__(self, batch: int, max_pages: int, page_size: int, num_pages: int, device: torch.device) -> None:
+        check_page_size(page_size, "PagedDecodeState")
+        assert batch >= 1 and max_pages >= 1 and num_pages > batch and num_pages * page_size < 2**31
+        self.batch, self.page, self.max_pages, self.num_pages = batch, page_size, max_pages, num_pages
+        self.capacity = max_pages * page_size
+        self.pos = torch.zeros(batch, dtype=torch.long, device=device)
+        self.k_range = torch.zeros(batch, 2, dtype=torch.int32, device=device)
+        self.block_table = torch.full((batch, max_pages), -1, dtype=torch.int32, device=device)
+        self.live = torch.zeros(batch, dtype=torch.long, device=device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        for b in range(batch):
+            self.park(b)
+
+    def park(self, b: int) -> None:
+        """Row b holds no request: position 0, one key, its parking page."""
+        row = torch.full((self.max_pages,), -1, dtype=torch.int32)
+        row[0] = b
+        self.block_table[b].copy_(row)
+        self.pos[b : b + 1].fill_(0)
+        self.k_range[b : b + 1, 1].fill_(1)
+        self.live[b : b + 1].fill_(0)
+
+    def assign(self, b: int, pages: Sequence[int], n_prompt: int) -> None:
+        """Row b takes a request of ``n_prompt`` cached tokens in ``pages`` (device copies from fresh host tensors)."""
+        assert len(pages) <= self.max_pages and 0 <= n_prompt < len(pages) * self.page
+        row = torch.full((self.max_pages,), -1, dtype=torch.int32)
+        row[: len(pages)] = torch.tensor(list(pages), dtype=torch.int32)
+        self.block_table[b].copy_(row)
+        self.pos[b : b + 1].fill_(n_prompt)
+        self.k_range[b : b + 1, 1].fill_(n_prompt + 1)
+        self.live[b : b + 1].fill_(1)
+
+    def set_page(self, b: int, index: int, page: int) -> None:
+        """One more page for row b.  The copy reads a tensor made for it, never host memory a later call rewrites."""
+        self.block_table[b, index : index + 1].copy_(torch.tensor([page], dtype=torch.int32))
+
+    def reset(self, prompt_lengths: Union[Sequence[int], torch.Tensor]) -> None:
+        """All rows back to their prompt lengths (a static batch rewinding after its capture passes)."""
+        if not isinstance(prompt_lengths, torch.Tensor):
+            prompt_lengths = torch.tensor(list(prompt_lengths), dtype=torch.long)
+        assert prompt_lengths.numel() == self.batch
+        self.pos.copy_(prompt_lengths)
+        self.k_range[:, 1].copy_(self.pos)
+        self.k_range[:, 1].add_(1)
+        self.err.zero_()
+
+    def check(self) -> None:
+        """Raises if a step ran a row at a position outside its pages or the rotary table."""
+        e = int(self.err.item())
+        if e & 1 or e & ~3:
+            raise RuntimeError("paged decode: a sequence's position fell outside its pages (or its block-table entry "
+                               "outside the pool) or the rotary table; its K/V rows were not written")
+        if e & 2:
+            raise RuntimeError(_NONFINITE_KV)
+
+    def advance(self) -> None:
+        self.pos.add_(self.live)
+        self.k_range[:, 1].add_(self.live)
+
+    def rows_of(self, pages: Sequence[int], n: int) -> torch.Tensor:
+        """Pool rows of the first ``n`` logical keys of a sequence that owns ``pages`` (host-built index)."""
+        assert n <= len(pages) * self.page
+        idx = (torch.tensor(list(pages), dtype=torch.long).view(-1, 1) * self.page
+               + torch.arange(self.page, dtype=torch.long).view(1, -1)).reshape(-1)[:n]
+        return idx.to(self.pos.device)
+
+    def _append_rows(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """(pool row each sequence writes, whether its position or table entry is out of range) for the unfused append:
+        an out-of-range sequence is clamped to a row it rewrites with the row's own content."""
+        pos = self.pos
+        bad = (pos < 0) | (pos >= self.capacity)
+        p = pos.clamp(0, self.capacity - 1)
+        entry = self.block_table.long().gather(1, (p // self.page).view(-1, 1)).view(-1)
+        bad = bad | (entry < 0) | (entry >= self.num_pages)
+        rows = entry.clamp(0, self.num_pages - 1) * self.page + p % self.page
+        return rows, bad
+
+
+class PagedKVCache(BatchStaticKVCache):
+    """``BatchStaticKVCache`` over a pool of pages: ``k`` / ``v`` ``[num_pages * page, nkv, hd]``, addressed through the
+    shared ``PagedDecodeState``'s block table (page ids mean the same in every layer's pool).  A sequence owns pages,
+    so its memory is its length rounded up to a page, and a row of the batch can be handed to another request in place.
+    ``append`` is the unfused write (CPU, fallbacks), equal to ``ext().rope_kv_append_paged``'s."""
+
+    def __init__(self, k: torch.Tensor, v: torch.Tensor, state: PagedDecodeState) -> None:
+        assert k.shape[0] == state.num_pages * state.page and v.shape == k.shape, (tuple(k.shape), state.num_pages)
+        self.k, self.v, self.state = k, v, state
+
+    @classmethod
+    def empty(cls, nkv: int, hd: int, dtype: torch.dtype, state: PagedDecodeState) -> "PagedKVCache":
+        """A zero-initialised pool (the parking pages must hold finite values)."""
+        shape = (state.num_pages * state.page, nkv, hd)
+        dev = state.pos.device
+        return cls(torch.zeros(shape, dtype=dtype, device=dev), torch.zeros(shape, dtype=dtype, device=dev), state)
+
+    def load_row(self, b: int, kv: "KVCache", pages: Sequence[int]) -> None:
+        """Copies the prompt a prefill left in ``kv`` into ``pages`` (logical order); the state is set by the caller."""
+        rows = self.state.rows_of(pages, kv.length)
+        self.k.index_copy_(0, rows, kv.k[: kv.length])
+        self.v.index_copy_(0, rows, kv.v[: kv.length])
+
+    def append(self, k: torch.Tensor, v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        st = self.state
+        assert k.shape[0] == st.batch, "batched decoding feeds one token per sequence and step"
+        rows, bad = st._append_rows()
+        keep = bad.view(-1, 1, 1)
+        self.k.index_copy_(0, rows, torch.where(keep, self.k.index_select(0, rows), k))
+        self.v.index_copy_(0, rows, torch.where(keep, self.v.index_select(0, rows), v))
+        st.err.bitwise_or_(bad.any().to(torch.int32))
+        return self.k, self.v, st.k_range
+
+    def bytes_per_page(self) -> int:
+        return 2 * self.state.page * self.k.shape[1] * self.k.shape[2] * self.k.element_size()
+
+
+class PagedKVCacheFP8(_FP8Rows, PagedKVCache):
+    """``PagedKVCache`` in the format of ``BatchStaticKVCacheFP8``: codes uint8 ``[num_pages * page, nkv, hd]`` and
+    scales fp32 ``[nkv, num_pages * page]`` (head-major; the 16-byte scale loads of the decode kernel lie inside one
+    page).  ``load_row`` quantises the prefilled rows as ``BatchStaticKVCacheFP8.from_caches`` does."""
+
+    def __init__(self, k: torch.Tensor, v: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                 state: PagedDecodeState, dtype: torch.dtype) -> None:
+        PagedKVCache.__init__(self, k, v, state)
+        self._set_scales(k_scale, v_scale, dtype)
+
+    @classmethod
+    def empty(cls, nkv: int, hd: int, dtype: torch.dtype, state: PagedDecodeState) -> "PagedKVCacheFP8":  # type: ignore[override]
+        dev = state.pos.device
+        _check_kv_dtype(dtype, dev.type != "cpu", "PagedKVCacheFP8")
+        like = torch.empty((0, nkv, hd), device=dev)
+        rows = state.num_pages * state.page
+        (kb, ks), (vb, vs) = cls._empty(rows, like), cls._empty(rows, like)
+        return cls(kb, vb, ks, vs, state, dtype)
+
+    def load_row(self, b: int, kv: "KVCache", pages: Sequence[int]) -> None:
+        rows = self.state.rows_of(pages, kv.length)
+        for codes, scale, src in ((self.k, self.k_scale, kv.k), (self.v, self.v_scale, kv.v)):
+            q, s = quant_ops.quantize_kv_rows(src[: kv.length].to(torch.bfloat16))
+            codes.index_copy_(0, rows, q)
+            scale.index_copy_(1, rows, s)
+
+    def append(self, k: torch.Tensor, v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        st = self.state
+        assert k.shape[0] == st.batch, "batched decoding feeds one token per sequence and step"
+        rows, bad = st._append_rows()
+        for codes, scale, x in ((self.k, self.k_scale, k), (self.v, self.v_scale, v)):
+            xb, nonfinite = quant_ops.sanitize_kv(x)
+            q, s = quant_ops.quantize_kv_rows(xb, check=False)
+            codes.index_copy_(0, rows, torch.where(bad.view(-1, 1, 1), codes.index_select(0, rows), q))
+            scale.index_copy_(1, rows, torch.where(bad.view(1, -1), scale.index_select(1, rows), s))
+            st.err.bitwise_or_(nonfinite.to(torch.int32) * 2)
+        st.err.bitwise_or_(bad.any().to(torch.int32))
+        return self.k, self.v, st.k_range
+
+    def bytes_per_page(self) -> int:
+        return self.state.page * self.bytes_per_token()
+
+
 def _fp8_scales(kv: Any) -> Optional[tuple[torch.Tensor, torch.Tensor]]:
-    return kv.scales if isinstance(kv, (StaticKVCacheFP8, BatchStaticKVCacheFP8)) else None
+    return kv.scales if isinstance(kv, (StaticKVCacheFP8, BatchStaticKVCacheFP8, PagedKVCacheFP8)) else None
 
 
 class _LoraUpInto(torch.autograd.Function):
@@ -830,7 +1048,8 @@ class ParallelSelfAttention(torch.nn.Module):
     def _decode_rope_append_batch(self, kv: BatchStaticKVCache, base: torch.Tensor, q: torch.Tensor, k: torch.Tensor,
                                   v: torch.Tensor, position_ids: Optional[torch.Tensor]) -> Optional[tuple]:
         """``_decode_rope_append`` for one token of each of the B sequences of a batched static cache, still ONE launch
-        (``ext().rope_kv_append_batch``): row b is rotated at ``pos[b]`` and appended to slab b.  The fourth entry of
+        (``ext().rope_kv_append_batch``): row b is rotated at ``pos[b]`` and appended to slab b -- or, for a
+        ``PagedKVCache``, to the page its block table names (``ext().rope_kv_append_paged``).  The fourth entry of
         the result is the cache's key ranges, not cu_seqlens."""
         re = self.rotary_embedding
         st = kv.state
@@ -847,8 +1066,13 @@ class ParallelSelfAttention(torch.nn.Module):
                 and all(t.stride(1) == hd and (st.batch == 1 or t.stride(0) == nh * hd) for t in (q, k, v))):
             return None
         sc = _fp8_scales(kv) or (None, None)
-        qr = ext().rope_kv_append_batch(base.view(st.batch, nh, hd), re.cos_table, re.sin_table, st.pos, nq, nkv,
-                                        re.dimensions, re.interleaved, kv.k, kv.v, st.err, st.capacity, sc[0], sc[1])
+        if isinstance(kv, PagedKVCache):  # the same kernel body; the row comes from the block table
+            qr = ext().rope_kv_append_paged(base.view(st.batch, nh, hd), re.cos_table, re.sin_table, st.pos, nq, nkv,
+                                            re.dimensions, re.interleaved, kv.k, kv.v, st.err, st.block_table, st.page,
+                                            sc[0], sc[1])
+        else:
+            qr = ext().rope_kv_append_batch(base.view(st.batch, nh, hd), re.cos_table, re.sin_table, st.pos, nq, nkv,
+                                            re.dimensions, re.interleaved, kv.k, kv.v, st.err, st.capacity, sc[0], sc[1])
         if qr is None:
             return None
         return qr, kv.k, kv.v, st.k_range
@@ -961,6 +1185,8 @@ class ParallelSelfAttention(torch.nn.Module):
                 assert s == 1 and b == batch_kv.state.batch, "batched decoding feeds one token per sequence"
                 common.update(cu_seqlens_k=None, key_ranges=cumulative_seq_lengths_key,
                               max_seqlen_k=batch_kv.state.capacity)
+                if isinstance(batch_kv, PagedKVCache):  # the keys are the pages the block table names
+                    common.update(block_table=batch_kv.state.block_table, page_size=batch_kv.state.page)
             if kv_scales is not None:
                 common.update(kv_scales=kv_scales)
             hidden = attn_ops.flash_attention(q, k, v, window=window, **common,

@@ -17,7 +17,7 @@ from __future__ import annotations
 import contextlib
 import math
 import threading
-from typing import Callable, Any, Iterator, Optional
+from typing import Callable, Any, Iterator, Optional, Sequence
 
 import torch
 
@@ -306,8 +306,43 @@ def rope_flash_attention(base: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v
                                 float(dropout_p), seed, -1 if local_heads is None else int(local_heads))
 
 
+def _check_pages(q, k, cu_seqlens_q, key_ranges, block_table, page_size) -> int:
+    """Validates ``block_table`` / ``page_size`` of :func:`flash_attention` (``ValueError``); returns the page size."""
+    if block_table is None or page_size is None:
+        raise ValueError("flash attention: block_table and page_size come together")
+    page = int(page_size)
+    if page <= 0 or page % 32:
+        raise ValueError(f"flash attention: page_size must be a positive multiple of 32 (the decode kernel's key tile), "
+                         f"got {page_size}")
+    if key_ranges is None:
+        raise ValueError("flash attention: block_table needs key_ranges ((0, length) per segment)")
+    nseg = cu_seqlens_q.numel() - 1
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != nseg or block_table.shape[1] < 1:
+        raise ValueError(f"flash attention: block_table must be int32 [segments, max_pages] = [{nseg}, *], got "
+                         f"{block_table.dtype} {tuple(block_table.shape)}")
+    if block_table.device != q.device:
+        raise ValueError(f"flash attention: block_table is on {block_table.device}, q on {q.device}")
+    if k.shape[0] == 0 or k.shape[0] % page:
+        raise ValueError(f"flash attention: with block_table, k / v hold whole pages; got {k.shape[0]} rows, page {page}")
+    return page
+
+
+def gather_pages(block_table: torch.Tensor, page: int, lengths: Sequence[int]) -> tuple[torch.Tensor, torch.Tensor]:
+    """Pool rows of the paged keys in logical order: ``(rows, key_ranges)`` such that ``k[rows]`` holds segment i's
+    ``lengths[i]`` keys back to back at ``key_ranges[i] = (start, length)`` (the dense form of a paged cache)."""
+    tab = block_table.tolist()
+    rows: list[int] = []
+    ranges = []
+    for i, n in enumerate(lengths):
+        n = max(0, min(int(n), len(tab[i]) * page))
+        ranges.append((len(rows), n))
+        rows.extend(tab[i][j // page] * page + j % page for j in range(n))
+    return (torch.tensor(rows, dtype=torch.long, device=block_table.device),
+            torch.tensor(ranges, dtype=torch.int32, device=block_table.device).view(-1, 2))
+
+
 def _flash_attention_ranges(q, k, v, cu_seqlens_q, key_ranges, max_seqlen_q, max_seqlen_k, softmax_scale, causal,
-                            window, p_drop, local_heads) -> torch.Tensor:
+                            window, p_drop, local_heads, block_table=None, page_size=0) -> torch.Tensor:
     """:func:`flash_attention` with ``key_ranges``: the flash-decoding kernel, or the dense reference on CPU."""
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
     win = -1 if window is None else int(window)
@@ -316,6 +351,9 @@ def _flash_attention_ranges(q, k, v, cu_seqlens_q, key_ranges, max_seqlen_q, max
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
         raise ValueError("flash attention: key_ranges are forward only (run under torch.no_grad())")
     if not use_native(q):
+        if block_table is not None:  # the dense reference on the gathered pages
+            rows, key_ranges = gather_pages(block_table, page_size, key_ranges[:, 1].tolist())
+            k, v = k.index_select(0, rows), v.index_select(0, rows)
         return attention_reference(q, k, v, cu_seqlens_q, None, scale, causal, win, local_heads=local_heads,
                                    key_ranges=key_ranges)
     if q.dtype not in (torch.bfloat16, torch.float16):
@@ -329,13 +367,15 @@ def _flash_attention_ranges(q, k, v, cu_seqlens_q, key_ranges, max_seqlen_q, max
         raise ValueError("flash attention: key_ranges are supported by the decode kernel only "
                          "(max_seqlen_q * q heads per kv head <= 32)")
     lh = -1 if local_heads is None else int(local_heads)
+    paged = () if block_table is None else (None, None, block_table, int(page_size))
     o, _ = ext().fa_fwd(q, k, v, cq, cq, int(max_seqlen_q), float(scale), bool(causal), win, 0.0, 0, lh,
-                        int(max_seqlen_k), key_ranges)
+                        int(max_seqlen_k), key_ranges, *paged)
     return o
 
 
 def _flash_attention_fp8_kv(q, k, v, kv_scales, cu_seqlens_q, cu_seqlens_k, key_ranges, max_seqlen_q, max_seqlen_k,
-                            softmax_scale, causal, window, p_drop, local_heads) -> torch.Tensor:
+                            softmax_scale, causal, window, p_drop, local_heads, block_table=None,
+                            page_size=0) -> torch.Tensor:
     """:func:`flash_attention` with ``kv_scales``: the flash-decoding kernel over FP8 K/V, or -- off the GPU -- the
     dense reference on the dequantised K/V."""
     from .quant import dequantize_kv_rows
@@ -359,6 +399,10 @@ def _flash_attention_fp8_kv(q, k, v, kv_scales, cu_seqlens_q, cu_seqlens_k, key_
     if not use_native(q):
         if q.dtype == torch.float16:
             raise ValueError("flash attention: FP8 K/V (kv_scales) needs bfloat16 queries, got torch.float16")
+        if block_table is not None:  # the dense reference on the gathered pages
+            rows, key_ranges = gather_pages(block_table, page_size, key_ranges[:, 1].tolist())
+            k, v = k.index_select(0, rows), v.index_select(0, rows)
+            k_scale, v_scale = k_scale.index_select(1, rows), v_scale.index_select(1, rows)
         kd, vd = dequantize_kv_rows(k, k_scale, q.dtype), dequantize_kv_rows(v, v_scale, q.dtype)
         return attention_reference(q, kd, vd, cu_seqlens_q, cu_seqlens_k, scale, causal, win, local_heads=local_heads,
                                    key_ranges=key_ranges)
@@ -380,7 +424,8 @@ def _flash_attention_fp8_kv(q, k, v, kv_scales, cu_seqlens_q, cu_seqlens_k, key_
             max_seqlen_k = int((ck[1:] - ck[:-1]).max().item())
     lh = -1 if local_heads is None else int(local_heads)
     o, _ = ext().fa_fwd(q, k, v, cq, ck, int(max_seqlen_q), float(scale), bool(causal), win, 0.0, 0, lh,
-                        int(max_seqlen_k), key_ranges, k_scale, v_scale)
+                        int(max_seqlen_k), key_ranges, k_scale, v_scale,
+                        *(() if block_table is None else (block_table, int(page_size))))
     return o
 
 
@@ -401,6 +446,8 @@ def flash_attention(
     deterministic: bool = True,
     key_ranges: Optional[torch.Tensor] = None,
     kv_scales: Optional[tuple[torch.Tensor, torch.Tensor]] = None,
+    block_table: Optional[torch.Tensor] = None,
+    page_size: Optional[int] = None,
 ) -> torch.Tensor:
     """q: [T, Hq, D]; k, v: [Tk, Hk, D] (unit last stride); cu_seqlens int32 [nseg+1].
 
@@ -416,14 +463,26 @@ def flash_attention(
     ``kv_scales`` = (k_scale, v_scale), float32 [Hk, Tk]: FP8 K/V.  ``k`` / ``v`` then hold OCP e4m3fn codes (uint8 or
     float8_e4m3fn) and row t of kv head h means ``code * scale[h, t]`` (``ops.quant.quantize_kv_rows``), with either
     key form.  bfloat16 queries, decode-sized calls, no dropout, forward only: anything else raises ``ValueError``.
-    The result is bit for bit the bf16 kernel's on the dequantised K/V; on CPU tensors the reference runs on them."""
+    The result is bit for bit the bf16 kernel's on the dequantised K/V; on CPU tensors the reference runs on them.
+
+    ``block_table`` int32 [nseg, max_pages] with ``page_size`` (a multiple of 32), together with ``key_ranges`` =
+    (0, length): paged K/V.  ``k`` / ``v`` (and ``kv_scales``) are a pool of pages of ``page_size`` rows and key j of
+    segment i is pool row ``block_table[i, j // page_size] * page_size + j % page_size``.  The restrictions of
+    ``key_ranges`` apply (``ValueError``).  For the same ``max_seqlen_k`` the result is bit for bit that of the
+    ``key_ranges`` call on a contiguous buffer holding the same rows in logical order; table entries past a segment's
+    length are never read and an entry outside the pool masks its keys.  On CPU tensors the dense reference runs on
+    the gathered pages."""
+    pages = {}
+    if block_table is not None or page_size is not None:
+        pages = dict(block_table=block_table,
+                     page_size=_check_pages(q, k, cu_seqlens_q, key_ranges, block_table, page_size))
     if kv_scales is not None:
         return _flash_attention_fp8_kv(q, k, v, kv_scales, cu_seqlens_q, cu_seqlens_k, key_ranges, max_seqlen_q,
                                        max_seqlen_k, softmax_scale, causal, window,
-                                       dropout_p if training else 0.0, local_heads)
+                                       dropout_p if training else 0.0, local_heads, **pages)
     if key_ranges is not None:
         return _flash_attention_ranges(q, k, v, cu_seqlens_q, key_ranges, max_seqlen_q, max_seqlen_k, softmax_scale,
-                                       causal, window, dropout_p if training else 0.0, local_heads)
+                                       causal, window, dropout_p if training else 0.0, local_heads, **pages)
     if cu_seqlens_k is None:
         cu_seqlens_k = cu_seqlens_q
         max_seqlen_k = max_seqlen_q

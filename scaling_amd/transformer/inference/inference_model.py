@@ -236,14 +236,19 @@ class TransformerInferenceModule(InferenceModule):
 
     def batch_decoder(self, max_tokens: int, input_tokens: Sequence[Sequence[int]],
                       sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
-                      skinny_gemm: bool = False, kv_cache: Optional[str] = None) -> Any:
+                      skinny_gemm: bool = False, kv_cache: Optional[str] = None, page_size: Optional[int] = None,
+                      num_pages: Optional[int] = None) -> Any:
         """Prefills the prompts one at a time (prompt b under ``cache_index`` b), draws every row's first token with
         ONE ``sample_fn`` call on the stacked prefill logits and returns the ``batch_decode.BatchDecoder`` that decodes
         them together (not yet captured: call ``capture()`` for graph replay).  ``skinny_gemm``: its steps run inside
         ``ops.gemm.skinny_gemm()`` (the MFMA weight-streaming kernels for up to 16 rows, see ``generate_batch``).
-        ``kv_cache``: None (bf16) or ``"fp8_e4m3"`` (see ``generate_batch``)."""
-        from ...core.nn.attention.attention import ParallelSelfAttention, check_kv_cache_scheme
+        ``kv_cache``: None (bf16) or ``"fp8_e4m3"`` (see ``generate_batch``).  ``page_size``: the same static batch over
+        the paged KV cache (``num_pages`` pages; see ``generate_batch``)."""
+        from ...core.nn.attention.attention import ParallelSelfAttention, check_kv_cache_scheme, check_page_size
         from .batch_decode import BatchDecoder
+
+        if page_size is not None:
+            check_page_size(page_size, "generate_batch")
 
         if check_kv_cache_scheme(kv_cache, "generate_batch") is not None:  # refuse before the prefills run
             for m in self.modules():
@@ -268,14 +273,14 @@ class TransformerInferenceModule(InferenceModule):
         prefill = torch.stack(last)  # [B, 1, V]
         first = sample_fn(prefill)
         return BatchDecoder(self, [len(p) for p in input_tokens], max_tokens, first, sample_fn, prefill,
-                            skinny_gemm=skinny_gemm, kv_cache=kv_cache)
+                            skinny_gemm=skinny_gemm, kv_cache=kv_cache, page_size=page_size, num_pages=num_pages)
 
     def generate_batch(self, max_tokens: int, input_texts: Optional[Sequence[str]] = None,
                        input_tokens: Optional[Sequence[Sequence[int]]] = None,
                        sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                        stop_tokens: Optional[Sequence[int]] = None,
                        use_cuda_graph: bool = False, skinny_gemm: bool = False,
-                       kv_cache: Optional[str] = None) -> list[CompletionOutput]:
+                       kv_cache: Optional[str] = None, page_size: Optional[int] = None) -> list[CompletionOutput]:
         """Completions for B prompts of any lengths, decoded together: one pass over the weights per step serves all
         B rows (``batch_decode.BatchDecoder``).  One device, always with the KV cache (flash attention kernel); the
         prompts are prefilled one at a time.  Stop tokens act per row: every row keeps stepping until all rows have
@@ -301,7 +306,13 @@ class TransformerInferenceModule(InferenceModule):
         -- written by the quantising RoPE + append kernel and read by the flash-decoding kernel
         (``BatchStaticKVCacheFP8``).  The prompts are prefilled against exact bf16 K/V and their rows quantised
         afterwards.  bf16 models on one device with the flash attention kernel; fp16, tensor parallelism and
-        ``key_query_norm`` raise ``ValueError``.  It composes with ``quantize_weights`` and ``skinny_gemm``."""
+        ``key_query_norm`` raise ``ValueError``.  It composes with ``quantize_weights`` and ``skinny_gemm``.
+
+        ``page_size`` (opt-in, a multiple of 32; default None, one slab per row): the same static batch over the paged
+        KV cache (``PagedKVCache``): each row owns ``ceil(length / page_size)`` pages of one pool instead of a slab of
+        ``longest prompt + max_tokens`` rows, and gets a page whenever it grows into one.  Same kernels with one table
+        lookup per 32-key tile; tokens and logits are the slab path's when ``longest prompt + max_tokens`` is a whole
+        number of pages (the split plans then coincide).  ``generate_continuous`` refills finished rows on top of it."""
         from ...core.nn.attention.attention import check_kv_cache_scheme
         from ...ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS
 
@@ -327,11 +338,75 @@ class TransformerInferenceModule(InferenceModule):
         if stop_tokens is None:
             assert self.tokenizer is not None, "If no tokenizer is provided, a stop token needs to be set manually"
             stop_tokens = [self.tokenizer.eos_token_id]
-        dec = self.batch_decoder(max_tokens, input_tokens, sample_fn, skinny_gemm=skinny_gemm, kv_cache=kv_cache)
+        dec = self.batch_decoder(max_tokens, input_tokens, sample_fn, skinny_gemm=skinny_gemm, kv_cache=kv_cache,
+                                 page_size=page_size)
         if use_cuda_graph:
             dec.capture()
         outs = []
         for tokens, logits in dec.run(stop_tokens):
+            text = self.tokenizer.decode(tokens) if self.tokenizer is not None else None
+            outs.append(CompletionOutput(completion_text=text, completion_tokens=tokens, completion_logits=logits))
+        return outs
+
+    def continuous_decoder(self, max_batch: int, page_size: int = 64, max_pages: int = 1,
+                           num_pages: Optional[int] = None,
+                           sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
+                           use_cuda_graph: bool = False, skinny_gemm: bool = False,
+                           kv_cache: Optional[str] = None, record_steps: int = 8) -> Any:
+        """The ``batch_decode.ContinuousBatchDecoder`` of this model for a serving loop (``admit`` / ``step`` /
+        ``release``, or ``serve``): ``max_batch`` rows over a paged KV cache whose requests take at most ``max_pages``
+        pages of ``page_size`` tokens; captured once when ``use_cuda_graph``.  See ``generate_continuous``."""
+        from .batch_decode import ContinuousBatchDecoder
+
+        if self.devices is None or len(self.devices) != 1:
+            raise RuntimeError("generate_continuous: the model must sit on one device")
+        return ContinuousBatchDecoder(self, max_batch, page_size=page_size, max_pages=max_pages, num_pages=num_pages,
+                                      sample_fn=sample_fn, skinny_gemm=skinny_gemm, kv_cache=kv_cache,
+                                      use_cuda_graph=use_cuda_graph, record_steps=record_steps)
+
+    def generate_continuous(self, max_tokens: Any, input_texts: Optional[Sequence[str]] = None,
+                            input_tokens: Optional[Sequence[Sequence[int]]] = None, max_batch: int = 4,
+                            page_size: int = 64, num_pages: Optional[int] = None,
+                            sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
+                            stop_tokens: Optional[Sequence[int]] = None, use_cuda_graph: bool = False,
+                            skinny_gemm: bool = False, kv_cache: Optional[str] = None) -> list[CompletionOutput]:
+        """Completions for N requests (N may exceed ``max_batch``) by continuous batching over a paged KV cache:
+        ``max_batch`` rows share every decode step, and a row whose request reaches a stop token or its own
+        ``max_tokens`` (an int, or one int per request) is refilled with the next request while the others go on
+        (``batch_decode.ContinuousBatchDecoder.serve``).  Requests are admitted in order and returned in order.
+
+        Each attention layer holds one pool of ``num_pages`` pages of ``page_size`` tokens (a multiple of 32); a request
+        owns ``ceil(length / page_size)`` of them.  ``num_pages=None`` sizes the pool for ``max_batch`` sequences of the
+        longest request (prompt + ``max_tokens``), plus one parking page per row.  A smaller pool raises
+        ``RuntimeError`` when it runs out (there is no preemption).  ``use_cuda_graph`` captures the step once for the
+        whole stream and has ``generate_batch``'s limits on ``max_batch`` (4, or 16 with ``skinny_gemm``); ``kv_cache``
+        as in ``generate_batch``.  Greedy completions equal ``generate``'s per prompt up to the rounding of the batched
+        kernels; with a seeded ``Sampler`` a draw depends on the row and the step a request happens to occupy."""
+        if (input_texts is None) == (input_tokens is None):
+            raise ValueError("generate_continuous: give either input_texts or input_tokens")
+        if input_texts is not None:
+            assert self.tokenizer is not None
+            input_tokens = [self.tokenizer.encode(t) for t in input_texts]
+        assert input_tokens is not None
+        if len(input_tokens) == 0:
+            raise ValueError("generate_continuous: no prompts")
+        limits = [int(max_tokens)] * len(input_tokens) if isinstance(max_tokens, int) else [int(m) for m in max_tokens]
+        if len(limits) != len(input_tokens):
+            raise ValueError("generate_continuous: max_tokens must be an int or one int per request")
+        if any(len(p) == 0 for p in input_tokens) or any(m < 1 for m in limits):
+            raise ValueError("generate_continuous: empty prompt or max_tokens < 1")
+        if stop_tokens is None:
+            assert self.tokenizer is not None, "If no tokenizer is provided, a stop token needs to be set manually"
+            stop_tokens = [self.tokenizer.eos_token_id]
+        from ...core.nn.attention.attention import check_page_size
+
+        check_page_size(page_size, "generate_continuous")
+        longest = max(len(p) + m for p, m in zip(input_tokens, limits))
+        dec = self.continuous_decoder(max_batch, page_size=page_size, max_pages=-(-longest // page_size),
+                                      num_pages=num_pages, sample_fn=sample_fn, use_cuda_graph=use_cuda_graph,
+                                      skinny_gemm=skinny_gemm, kv_cache=kv_cache)
+        outs = []
+        for tokens, logits in dec.serve(list(zip(input_tokens, limits)), stop_tokens):
             text = self.tokenizer.decode(tokens) if self.tokenizer is not None else None
             outs.append(CompletionOutput(completion_text=text, completion_tokens=tokens, completion_logits=logits))
         return outs

@@ -13,7 +13,11 @@ plus scales for FP8).
 ``slab`` is the rows between two sequences' first rows: ``ctx`` (every slab starts at a multiple of four rows, so the
 four scales of a register group sit at a 16-byte aligned address) and, for B = 16, ``ctx + 1`` -- what the batched
 decoder's capacity (longest prompt + max_tokens) is in general: slabs start at arbitrary rows and most groups are at
-dword-aligned addresses only."""
+dword-aligned addresses only.
+
+``paged`` (the ``slab = ctx`` lines): the same buffers read as a pool of ``PAGE``-row pages (default 64) through a block
+table that names the pages in a shuffled order -- the paged form of the same call, alternating with the slab call in the
+same pass.  Both read the same bytes; the difference is the table lookup per 32-key tile and the page order."""
 from __future__ import annotations
 
 import os
@@ -94,13 +98,40 @@ def bench(ext, B: int, ctx: int, slab: int, passes: int, reps: int, scale: float
         kc, ks, vc, vs = f8[i % n]
         return ext().fa_fwd(q, kc, vc, cu_q, cu_q, 1, scale, True, -1, 0.0, 0, -1, slab, kr, ks, vs)
 
+    page = int(os.environ.get("PAGE", "64"))
+    paged = slab == ctx and ctx % page == 0
+    if paged:  # the same buffers as a pool of pages, handed out in a shuffled order
+        gp = torch.Generator().manual_seed(1)
+        table = torch.randperm(rows // page, generator=gp).to(torch.int32).view(B, ctx // page).to(dev)
+        kr0 = torch.tensor([[0, ctx]] * B, device=dev, dtype=torch.int32)
+
+        def run16p(i):
+            k, v = bf[i % n]
+            return ext().fa_fwd(q, k, v, cu_q, cu_q, 1, scale, True, -1, 0.0, 0, -1, slab, kr0, None, None, table, page)
+
+        def run8p(i):
+            kc, ks, vc, vs = f8[i % n]
+            return ext().fa_fwd(q, kc, vc, cu_q, cu_q, 1, scale, True, -1, 0.0, 0, -1, slab, kr0, ks, vs, table, page)
+
+        # the paged call against the slab call on the rows gathered in logical order
+        idx = (table.long().view(-1, 1) * page + torch.arange(page, device=dev).view(1, -1)).view(-1)
+        k0, v0 = bf[0]
+        ref = ext().fa_fwd(q, k0[idx], v0[idx], cu_q, cu_q, 1, scale, True, -1, 0.0, 0, -1, slab, kr)[0]
+        same_p = torch.equal(run16p(0)[0], ref) and torch.equal(run8p(0)[0], ref)
+        del idx, ref
     same = torch.equal(run16(0)[0], run8(0)[0])
     for p in range(passes):
         us16 = timeit(run16, reps)
+        us16p = timeit(run16p, reps) if paged else 0.0
         us8 = timeit(run8, reps)
-        print(f"B={B:2d} ctx={ctx:5d} slab={slab:5d} reps={reps:4d} pass {p}  bf16 {us16:8.2f} us {nb16 / us16 / 1e6:5.2f} TB/s   "
-              f"fp8 {us8:8.2f} us {nb8 / us8 / 1e6:5.2f} TB/s   bf16/fp8 time {us16 / us8:4.2f}  "
-              f"outputs equal {same}", flush=True)
+        us8p = timeit(run8p, reps) if paged else 0.0
+        line = (f"B={B:2d} ctx={ctx:5d} slab={slab:5d} reps={reps:4d} pass {p}  bf16 {us16:8.2f} us {nb16 / us16 / 1e6:5.2f} TB/s   "
+                f"fp8 {us8:8.2f} us {nb8 / us8 / 1e6:5.2f} TB/s   bf16/fp8 time {us16 / us8:4.2f}  "
+                f"outputs equal {same}")
+        if paged:
+            line += (f"   paged({page}) bf16 {us16p:8.2f} us x{us16p / us16:5.3f}   fp8 {us8p:8.2f} us x{us8p / us8:5.3f}  "
+                     f"paged equal gathered slab {same_p}")
+        print(line, flush=True)
     del f8, bf
     torch.cuda.empty_cache()
 

@@ -2,7 +2,7 @@
 
     python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64] [--sampler T,K,P | torch:T,K,P]
                                  [--weights fp8_e4m3 [--lm-head]] [--batch B [--skinny]]
-                                 [--kv-cache bf16,fp8_e4m3 [--rounds N]]
+                                 [--kv-cache bf16,fp8_e4m3 [--rounds N]] [--paged 0,64] [--continuous N]
 
 ``--batch B`` times batched generation instead (``generate_batch`` / ``BatchDecoder``): B random prompts of lengths
 ``prompt, prompt - 7, prompt - 14, ...`` decoded together; ms per step, tokens/s summed over the rows, and (B <= 4:
@@ -16,6 +16,16 @@ their bf16 parameters).
 ``--kv-cache fp8_e4m3`` (with ``--batch``) decodes over the FP8 KV cache (``generate_batch(kv_cache=...)``); a comma
 list such as ``bf16,fp8_e4m3`` measures the settings alternately in this process, ``--rounds`` times, one JSON line
 each.  Every line carries ``kv_cache`` and ``kv_bytes_per_token`` (K and V of all layers).
+
+``--paged PAGE`` (with ``--batch``) runs the static batch over the paged KV cache (``batch_decoder(page_size=PAGE)``); a
+comma list such as ``0,64`` (0: the slab cache) measures the settings alternately in this process, ``--rounds`` times.
+
+``--continuous N`` (with ``--batch B --skinny``, B the number of rows): a seeded stream of N requests (prompt lengths
+``prompt - 7 * (i % 16)``, ``max_tokens`` uniform in ``--spread`` = 32,256, no stop tokens) served by continuous batching
+over the paged cache (``ContinuousBatchDecoder.serve``, page size ``--paged`` or 64, one captured graph) and, for
+comparison, by ``batch_decoder`` over the same requests in arrival-order groups of B, each group running to its longest
+``max_tokens``.  Wall time covers prefills and decoding of both (graph captures excluded); tokens are the requested ones.
+Also prints the KV memory each held: pages in use at the peak x bytes per page against B slabs of ``cap`` rows.
 
 ``--sampler 0.8,40,0.95`` decodes with the fused ``Sampler`` (temperature, top-k, top-p) in both loops;
 ``--sampler torch:0.8,40,0.95`` times the eager loop with the torch composition
@@ -52,7 +62,13 @@ def main() -> None:
     p.add_argument("--kv-cache", default="bf16", help="with --batch: bf16, fp8_e4m3 (generate_batch(kv_cache=...)), or a "
                    "comma list measured alternately in this process (one JSON line per setting and round)")
     p.add_argument("--rounds", type=int, default=1, help="with --batch: repeat the --kv-cache list this many times")
+    p.add_argument("--paged", default="0", help="with --batch: page size of the paged KV cache (0: slabs), or a comma list "
+                   "measured alternately")
+    p.add_argument("--continuous", type=int, default=0, help="with --batch B --skinny: serve N requests by continuous "
+                   "batching and by static groups of B")
+    p.add_argument("--spread", default="32,256", help="with --continuous: range of the requests' max_tokens")
     a = p.parse_args()
+    a.page_list = [int(x) or None for x in a.paged.split(",")]
     a.kv_list = [None if k == "bf16" else k for k in a.kv_cache.split(",")]
     if a.kv_list != [None] and a.batch < 1:
         raise SystemExit("--kv-cache needs --batch (the single-sequence eager loop keeps a growing bf16 cache)")
@@ -101,7 +117,11 @@ def main() -> None:
             raise SystemExit("--batch needs a graph-safe sampler (greedy or T,K,P)")
         for _ in range(a.rounds):
             for kv in a.kv_list:
-                batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv)
+                if a.continuous:
+                    continuous_bench(m, a, arch, sample_fn, timed, kv)
+                    continue
+                for page in a.page_list:
+                    batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv, page)
         return
 
     m.generate(4, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn)  # warm-up (library handles, tables)
@@ -141,9 +161,57 @@ def main() -> None:
     }), flush=True)
 
 
-def batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv=None) -> None:
+def continuous_bench(m, a, arch, sample_fn, timed, kv=None) -> None:
+    """``--continuous N``: total generated tokens / wall time of continuous batching against static groups of B."""
+    import random
+
+    B, N = a.batch, a.continuous
+    page = a.page_list[0] or 64
+    lo, hi = (int(x) for x in a.spread.split(","))
+    rng = random.Random(0)
+    gen = torch.Generator().manual_seed(1)
+    reqs = [(torch.randint(1, arch.vocab_size, (max(1, a.prompt - 7 * (i % 16)),), generator=gen).tolist(),
+             rng.randint(lo, hi)) for i in range(N)]
+    total = sum(mt for _, mt in reqs)
+    nkv = arch.attention_num_kv_heads or arch.num_attention_heads
+    hd = arch.hidden_size // arch.num_attention_heads
+    per_token = arch.num_layers * 2 * nkv * (2 * hd if kv is None else hd + 4)
+    kw = dict(skinny_gemm=a.skinny, kv_cache=kv)
+    graph = next(m.parameters()).is_cuda
+    longest = max(len(p) + mt for p, mt in reqs)
+    m.generate_continuous(4, input_tokens=[p for p, _ in reqs[:B]], max_batch=B, page_size=page, stop_tokens=[],
+                          use_cuda_graph=graph, sample_fn=sample_fn, **kw)  # warm-up
+    dec = m.continuous_decoder(B, page_size=page, max_pages=-(-longest // page), sample_fn=sample_fn, use_cuda_graph=graph,
+                               **kw)
+    tcont, out = timed(lambda: dec.serve(reqs, []))
+    assert [len(t) for t, _ in out] == [mt for _, mt in reqs]
+    tstat, cap_rows, steps_static = 0.0, 0, 0
+    for g0 in range(0, N, B):
+        group = reqs[g0 : g0 + B]
+        mt = max(x for _, x in group)
+        tp, sdec = timed(lambda: m.batch_decoder(mt, [p for p, _ in group], sample_fn, **kw))
+        if graph:
+            sdec.capture()
+        tr, _ = timed(lambda: sdec.run([], check_every=mt))
+        tstat += tp + tr
+        steps_static += mt - 1
+        cap_rows = max(cap_rows, len(group) * sdec.capacity)
+    print(json.dumps({
+        "metric": "continuous vs static batching, generated tokens/s", "requests": N, "rows": B, "model": a.model,
+        "layers": arch.num_layers, "prompt": a.prompt, "max_tokens_range": [lo, hi], "tokens": total, "page": page,
+        "kv_cache": kv or "bf16", "skinny_gemm": a.skinny,
+        "continuous_s": round(tcont, 3), "continuous_tokens_per_s": round(total / tcont, 1), "continuous_steps": dec.steps_run,
+        "static_s": round(tstat, 3), "static_tokens_per_s": round(total / tstat, 1), "static_steps": steps_static,
+        "speedup": round(tstat / tcont, 2),
+        "continuous_peak_pages": dec.allocator.peak_in_use + B,
+        "continuous_kv_gib": round((dec.allocator.peak_in_use + B) * page * per_token / 2**30, 3),
+        "static_kv_rows": cap_rows, "static_kv_gib": round(cap_rows * per_token / 2**30, 3),
+    }), flush=True)
+
+
+def batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv=None, page=None) -> None:
     """``--batch B``: per-step time of the batched decode loop (prefills and capture excluded); ``kv``: the KV cache
-    scheme (None: bf16)."""
+    scheme (None: bf16); ``page``: the paged cache's page size (None: slabs)."""
     from scaling_amd.ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS
 
     B, steps = a.batch, a.tokens
@@ -153,8 +221,9 @@ def batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv=None) -> None:
     nkv = arch.attention_num_kv_heads or arch.num_attention_heads
     hd = arch.hidden_size // arch.num_attention_heads
     kv_bytes = arch.num_layers * 2 * nkv * (2 * hd if kv is None else hd + 4)  # K and V, all layers, one token
-    m.generate_batch(4, input_tokens=prompts, stop_tokens=[], sample_fn=sample_fn, skinny_gemm=a.skinny, kv_cache=kv)  # warm-up
-    dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv)
+    m.generate_batch(4, input_tokens=prompts, stop_tokens=[], sample_fn=sample_fn, skinny_gemm=a.skinny, kv_cache=kv,
+                     page_size=page)  # warm-up
+    dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv, page_size=page)
     te, eager = timed(lambda: dec.run([], check_every=steps + 1))
     eager_ms = 1000.0 * te / steps
     weights = sum(p.numel() * p.element_size() for p in m.parameters())
@@ -162,10 +231,11 @@ def batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv=None) -> None:
         weights = weights - quantised["bf16_bytes"] + quantised["fp8_bytes"]
     res = {"metric": "batched decode ms/step", "batch": B, "sampler": mode, "model": a.model, "layers": arch.num_layers,
            "prompt": a.prompt, "tokens": steps, "weights": a.weights, "skinny_gemm": a.skinny, "kv_cache": kv or "bf16",
+           "page_size": page or 0,
            "kv_bytes_per_token": kv_bytes, "eager_ms_per_step": round(eager_ms, 3),
            "eager_tokens_per_s": round(B * 1000.0 / eager_ms, 1), "weights_gib": round(weights / 2**30, 2)}
     if B <= (SKINNY_MAX_ROWS if a.skinny else GEMV_MAX_ROWS):
-        dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv)
+        dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv, page_size=page)
         tc, _ = timed(dec.capture)
         tg, graph = timed(lambda: dec.run([], check_every=steps + 1))
         graph_ms = 1000.0 * tg / steps
