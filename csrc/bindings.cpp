@@ -445,11 +445,28 @@ at::Tensor transpose2d(const at::Tensor& x) {
 //  * FP8 (the gemv_w8* names): W = scale[n] * Q[n, :], Q [N, K] OCP e4m3fn codes (float8_e4m3fn, or the same bytes
 //    as uint8), scale [N] fp32 powers of two (ops/quant.py); x bf16.  16-byte pieces of 16 codes: K % 16 == 0, Q rows
 //    a multiple of 16 bytes apart, 16-byte aligned bases.
+//  * MXFP4 (the gemv_w4* names; scale is then the 2-D tensor of block scales): codes [N, K / 2] uint8, two OCP e2m1
+//    codes per byte, scales [N, K / 32] uint8 (e8m0), x bf16 [M, K].  16-byte pieces of 32 codes = one block:
+//    K % 32 == 0, code rows exactly K / 2 bytes apart (whole rows of the group's buffer), scale rows contiguous.
 // Each pair of bound functions is one worker; name is the bound function's, for the error messages.
 // The skinny* names are the same layers on the MFMA kernel (skinny.hip): the same operand rules with M <= 16 (skinny
 // = true below), the same signatures and return conventions; there is no RoPE form.
 constexpr int64_t kGemvRows = 4, kSkinnyRows = 16;
+// (a 2-D scale tensor marks the MXFP4 format for the shared workers below; the _w8 entry points take 1-D scales only)
+bool is_w4(const at::Tensor* scale) { return scale && scale->dim() == 2; }
+bool gemv_w4_operands_ok(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S, bool skinny) {
+    if (!(x.is_cuda() && C.is_cuda() && S.is_cuda() && x.dim() == 2 && C.dim() == 2 && S.dim() == 2)) return false;
+    if (C.device() != x.device() || S.device() != x.device()) return false;
+    if (x.scalar_type() != at::kBFloat16 || C.scalar_type() != at::kByte || S.scalar_type() != at::kByte) return false;
+    const int64_t K = x.size(1), N = C.size(0);
+    if (K < 32 || K % 32 != 0 || N < 1 || C.size(1) != K / 2 || S.size(0) != N || S.size(1) != K / 32) return false;
+    if (x.size(0) < 1 || x.size(0) > (skinny ? kSkinnyRows : kGemvRows)) return false;
+    if (x.stride(1) != 1 || (x.size(0) > 1 && x.stride(0) % 8 != 0)) return false;
+    if (C.stride(1) != 1 || C.stride(0) != K / 2 || !S.is_contiguous()) return false;
+    return (uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)C.data_ptr() % 16 == 0;
+}
 bool gemv_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale, bool skinny = false) {
+    if (is_w4(scale)) return gemv_w4_operands_ok(x, W, *scale, skinny);
     const int64_t P = scale ? 16 : 8;  // weights per 16-byte piece
     if (!(x.is_cuda() && W.is_cuda() && x.dim() == 2 && W.dim() == 2)) return false;
     if (scale) {
@@ -475,26 +492,29 @@ bool gemv_norm_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::T
     return gamma.is_cuda() && gamma.dim() == 1 && gamma.numel() == x.size(1) && gamma.is_contiguous() &&
            gamma.scalar_type() == x.scalar_type() && (uintptr_t)gamma.data_ptr() % 16 == 0;
 }
-const float* scale_ptr(const at::Tensor* scale) { return scale ? scale->data_ptr<float>() : nullptr; }
+const float* scale_ptr(const at::Tensor* scale) { return scale && !is_w4(scale) ? scale->data_ptr<float>() : nullptr; }
+const uint8_t* bscale_ptr(const at::Tensor* scale) { return is_w4(scale) ? scale->data_ptr<uint8_t>() : nullptr; }
 // one launcher for both kernels (epi 3, the RoPE step, is gemv's alone and launched where it is bound)
 void gemv_launch(bool skinny, int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale,
                  const void* b, void* y, int64_t ldy, int N, int K, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
-                 const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f) {
+                 const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
+                 const uint8_t* bscale = nullptr) {
     if (skinny)
         sa_launch::skinny(dtype, M, x, ldx, W, ldw, scale, b, y, ldy, N, K, cur_stream(), epi, res, ldr, norm_w, norm_add,
-                          norm_sum, eps);
+                          norm_sum, eps, bscale);
     else
         sa_launch::gemv(dtype, M, x, ldx, W, ldw, scale, b, y, ldy, N, K, cur_stream(), epi, res, ldr, norm_w, norm_add,
-                        norm_sum, eps);
+                        norm_sum, eps, nullptr, bscale);
 }
 
 at::Tensor gemv_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
                      const c10::optional<at::Tensor>& bias, bool skinny = false) {
     TORCH_CHECK(gemv_operands_ok(x, W, scale, skinny), name, ": unsupported operands ",
-                scale ? "(x bf16 [M, K], Q e4m3fn [N, K], scale fp32 [N], K % 16 == 0, 16-byte aligned rows"
+                is_w4(scale) ? "(x bf16 [M, K], codes uint8 [N, K / 2] in whole rows, scales uint8 [N, K / 32] contiguous, K % 32 == 0"
+                : scale ? "(x bf16 [M, K], Q e4m3fn [N, K], scale fp32 [N], K % 16 == 0, 16-byte aligned rows"
                       : "(x [M, K], W [N, K], bf16/fp16, K % 8 == 0, aligned", skinny ? ", M <= 16)" : ", M <= 4)");
     const at::DeviceGuard g(x.device());
-    const int64_t M = x.size(0), N = W.size(0), K = W.size(1);
+    const int64_t M = x.size(0), N = W.size(0), K = x.size(1);
     const void* bp = nullptr;
     at::Tensor bc;
     if (bias.has_value() && bias->defined()) {
@@ -504,20 +524,21 @@ at::Tensor gemv_impl(const char* name, const at::Tensor& x, const at::Tensor& W,
     }
     auto y = at::empty({M, N}, x.options());
     gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), bp,
-                y.data_ptr(), N, (int)N, (int)K);
+                y.data_ptr(), N, (int)N, (int)K, 0, nullptr, 0, nullptr, nullptr, nullptr, 0.f, bscale_ptr(scale));
     return y;
 }
 // decode epilogues: y = rnd(x W^T) + res  (res [M, N]) ...
 at::Tensor gemv_residual_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
                               const at::Tensor& res, bool skinny = false) {
     TORCH_CHECK(gemv_operands_ok(x, W, scale, skinny), name, ": unsupported operands");
-    const int64_t M = x.size(0), N = W.size(0), K = W.size(1);
+    const int64_t M = x.size(0), N = W.size(0), K = x.size(1);
     TORCH_CHECK(res.is_cuda() && res.dim() == 2 && res.size(0) == M && res.size(1) == N && res.stride(1) == 1 &&
                     res.scalar_type() == x.scalar_type(), name, ": res must be [M, N] of the input dtype");
     const at::DeviceGuard g(x.device());
     auto y = at::empty({M, N}, x.options());
     gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
-                y.data_ptr(), N, (int)N, (int)K, 1, res.data_ptr(), res.stride(0));
+                y.data_ptr(), N, (int)N, (int)K, 1, res.data_ptr(), res.stride(0), nullptr, nullptr, nullptr, 0.f,
+                bscale_ptr(scale));
     return y;
 }
 // ... and SwiGLU over W = [gate; up] ([2F, K]): y[:, n] = silu(x W_gate^T)[n] * (x W_up^T)[n], rounded as gemv + swiglu
@@ -525,11 +546,11 @@ at::Tensor gemv_residual_impl(const char* name, const at::Tensor& x, const at::T
 at::Tensor gemv_swiglu_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
                             bool skinny = false) {
     TORCH_CHECK(gemv_operands_ok(x, W, scale, skinny) && W.size(0) % 2 == 0, name, ": unsupported operands");
-    const int64_t M = x.size(0), F = W.size(0) / 2, K = W.size(1);
+    const int64_t M = x.size(0), F = W.size(0) / 2, K = x.size(1);
     const at::DeviceGuard g(x.device());
     auto y = at::empty({M, F}, x.options());
     gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
-                y.data_ptr(), F, (int)F, (int)K, 2, nullptr, 0);
+                y.data_ptr(), F, (int)F, (int)K, 2, nullptr, 0, nullptr, nullptr, nullptr, 0.f, bscale_ptr(scale));
     return y;
 }
 // ... with the RMSNorm in front fused into the same pass: s = x (+ add); y = gemv(rms_norm(s, gamma, eps), W) with
@@ -540,7 +561,7 @@ std::vector<at::Tensor> gemv_norm_impl(const char* name, const at::Tensor& x, co
                                        int64_t epi, bool skinny = false) {
     TORCH_CHECK(gemv_norm_operands_ok(x, W, scale, gamma, skinny) && (epi == 0 || (epi == 2 && W.size(0) % 2 == 0)), name,
                 ": unsupported operands");
-    const int64_t M = x.size(0), K = W.size(1), N = epi == 2 ? W.size(0) / 2 : W.size(0);
+    const int64_t M = x.size(0), K = x.size(1), N = epi == 2 ? W.size(0) / 2 : W.size(0);
     const at::DeviceGuard g(x.device());
     at::Tensor s = x;
     const void* ap = nullptr;
@@ -554,7 +575,7 @@ std::vector<at::Tensor> gemv_norm_impl(const char* name, const at::Tensor& x, co
     auto y = at::empty({M, N}, x.options());
     gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
                 y.data_ptr(), N, (int)N, (int)K, (int)epi, nullptr, 0, gamma.data_ptr(), ap, ap ? s.data_ptr() : nullptr,
-                (float)eps);
+                (float)eps, bscale_ptr(scale));
     return {s, y};
 }
 
@@ -573,21 +594,27 @@ std::vector<at::Tensor> gemv_norm(const at::Tensor& x, c10::optional<at::Tensor>
                                   double eps, const at::Tensor& W, int64_t epi) {
     return gemv_norm_impl("gemv_norm", x, add, gamma, eps, W, nullptr, epi);
 }
-bool gemv_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) { return gemv_operands_ok(x, Q, &scale); }
+bool gemv_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    return scale.dim() == 1 && gemv_operands_ok(x, Q, &scale);
+}
 at::Tensor gemv_w8(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, c10::optional<at::Tensor> bias) {
+    TORCH_CHECK(scale.dim() == 1, "gemv_w8: scale must be one fp32 per row [N]");
     return gemv_impl("gemv_w8", x, Q, &scale, bias);
 }
 at::Tensor gemv_w8_residual(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& res) {
+    TORCH_CHECK(scale.dim() == 1, "gemv_w8_residual: scale must be one fp32 per row [N]");
     return gemv_residual_impl("gemv_w8_residual", x, Q, &scale, res);
 }
 at::Tensor gemv_w8_swiglu(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    TORCH_CHECK(scale.dim() == 1, "gemv_w8_swiglu: scale must be one fp32 per row [N]");
     return gemv_swiglu_impl("gemv_w8_swiglu", x, Q, &scale);
 }
 bool gemv_w8_norm_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& gamma) {
-    return gemv_norm_operands_ok(x, Q, &scale, gamma);
+    return scale.dim() == 1 && gemv_norm_operands_ok(x, Q, &scale, gamma);
 }
 std::vector<at::Tensor> gemv_w8_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
                                      double eps, const at::Tensor& Q, const at::Tensor& scale, int64_t epi) {
+    TORCH_CHECK(scale.dim() == 1, "gemv_w8_norm: scale must be one fp32 per row [N]");
     return gemv_norm_impl("gemv_w8_norm", x, add, gamma, eps, Q, &scale, epi);
 }
 
@@ -607,22 +634,61 @@ std::vector<at::Tensor> skinny_norm(const at::Tensor& x, c10::optional<at::Tenso
                                     double eps, const at::Tensor& W, int64_t epi) {
     return gemv_norm_impl("skinny_norm", x, add, gamma, eps, W, nullptr, epi, true);
 }
-bool skinny_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) { return gemv_operands_ok(x, Q, &scale, true); }
+bool skinny_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    return scale.dim() == 1 && gemv_operands_ok(x, Q, &scale, true);
+}
 at::Tensor skinny_w8(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, c10::optional<at::Tensor> bias) {
+    TORCH_CHECK(scale.dim() == 1, "skinny_w8: scale must be one fp32 per row [N]");
     return gemv_impl("skinny_w8", x, Q, &scale, bias, true);
 }
 at::Tensor skinny_w8_residual(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& res) {
+    TORCH_CHECK(scale.dim() == 1, "skinny_w8_residual: scale must be one fp32 per row [N]");
     return gemv_residual_impl("skinny_w8_residual", x, Q, &scale, res, true);
 }
 at::Tensor skinny_w8_swiglu(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    TORCH_CHECK(scale.dim() == 1, "skinny_w8_swiglu: scale must be one fp32 per row [N]");
     return gemv_swiglu_impl("skinny_w8_swiglu", x, Q, &scale, true);
 }
 bool skinny_w8_norm_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& gamma) {
-    return gemv_norm_operands_ok(x, Q, &scale, gamma, true);
+    return scale.dim() == 1 && gemv_norm_operands_ok(x, Q, &scale, gamma, true);
 }
 std::vector<at::Tensor> skinny_w8_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
                                        double eps, const at::Tensor& Q, const at::Tensor& scale, int64_t epi) {
+    TORCH_CHECK(scale.dim() == 1, "skinny_w8_norm: scale must be one fp32 per row [N]");
     return gemv_norm_impl("skinny_w8_norm", x, add, gamma, eps, Q, &scale, epi, true);
+}
+
+// MXFP4 weights on both kernels: (codes [N, K / 2], scales [N, K / 32]) in place of (Q, scale)
+#define SA_W4_ENTRY(pre, sk)                                                                                           \
+    bool pre##_w4_ok(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S) {                                  \
+        return S.dim() == 2 && gemv_operands_ok(x, C, &S, sk);                                                         \
+    }                                                                                                                  \
+    at::Tensor pre##_w4(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S, c10::optional<at::Tensor> bias) { \
+        TORCH_CHECK(S.dim() == 2, #pre "_w4: scales must be [N, K / 32]");                                             \
+        return gemv_impl(#pre "_w4", x, C, &S, bias, sk);                                                              \
+    }                                                                                                                  \
+    at::Tensor pre##_w4_residual(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S, const at::Tensor& res) { \
+        TORCH_CHECK(S.dim() == 2, #pre "_w4_residual: scales must be [N, K / 32]");                                    \
+        return gemv_residual_impl(#pre "_w4_residual", x, C, &S, res, sk);                                             \
+    }                                                                                                                  \
+    at::Tensor pre##_w4_swiglu(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S) {                        \
+        TORCH_CHECK(S.dim() == 2, #pre "_w4_swiglu: scales must be [2F, K / 32]");                                     \
+        return gemv_swiglu_impl(#pre "_w4_swiglu", x, C, &S, sk);                                                      \
+    }                                                                                                                  \
+    bool pre##_w4_norm_ok(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S, const at::Tensor& gamma) {    \
+        return S.dim() == 2 && gemv_norm_operands_ok(x, C, &S, gamma, sk);                                             \
+    }                                                                                                                  \
+    std::vector<at::Tensor> pre##_w4_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma, \
+                                          double eps, const at::Tensor& C, const at::Tensor& S, int64_t epi) {         \
+        TORCH_CHECK(S.dim() == 2, #pre "_w4_norm: scales must be [N, K / 32]");                                        \
+        return gemv_norm_impl(#pre "_w4_norm", x, add, gamma, eps, C, &S, epi, sk);                                    \
+    }
+SA_W4_ENTRY(gemv, false)
+SA_W4_ENTRY(skinny, true)
+#undef SA_W4_ENTRY
+void gemv_w4_rule(int64_t rpw, int64_t ks) {
+    TORCH_CHECK((rpw == 0 && ks == 0) || ((rpw == 1 || rpw == 2 || rpw == 4) && (ks == 1 || ks == 4)), "gemv_w4_rule");
+    sa_launch::gemv_w4_rule((int)rpw, (int)ks);
 }
 
 // graph-decode q/k/v step in ONE launch: q = RoPE(rms_norm(x) Wq^T) is returned, RoPE(rms_norm(x) Wk^T) and
@@ -1065,6 +1131,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "in one launch; returns q or None");
     m.def("gemv_norm", &gemv_norm, "(s, gemv(rms_norm(s), W)) with s = x (+ add); epi 0 plain, 2 SwiGLU (decode)",
           py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("W"), py::arg("epi") = 0);
+#define SA_W4_DEF(pre)                                                                                                  \
+    m.def(#pre "_w4_ok", &pre##_w4_ok, "whether the MXFP4-weight kernel supports these operands");                      \
+    m.def(#pre "_w4", &pre##_w4, "y = x dequant(codes, scales)^T (+ b): e2m1 codes [N, K / 2], e8m0 scales [N, K / 32]", \
+          py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("bias") = py::none());                             \
+    m.def(#pre "_w4_residual", &pre##_w4_residual, "the MXFP4 layer + res (decode down / o-projection + residual)");    \
+    m.def(#pre "_w4_swiglu", &pre##_w4_swiglu, "silu(x Wg^T) * (x Wu^T) over MXFP4 [Wg; Wu] (decode)");                 \
+    m.def(#pre "_w4_norm_ok", &pre##_w4_norm_ok, "whether the MXFP4 norm form supports these operands");                \
+    m.def(#pre "_w4_norm", &pre##_w4_norm, "(s, y) with s = x (+ add), y the MXFP4 layer of rms_norm(s); epi 0 plain, 2 SwiGLU", \
+          py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("codes"), py::arg("scales"), py::arg("epi") = 0);
+    SA_W4_DEF(gemv)
+    SA_W4_DEF(skinny)
+#undef SA_W4_DEF
+    m.def("gemv_w4_rule", &gemv_w4_rule, "A/B switch of tools/gemv_bench.py: force the MXFP4 GEMV's (rows per wave, waves per row); (0, 0) restores its rules");
     m.def("skinny_ok", &skinny_ok, "whether skinny supports these operands");
     m.def("skinny", &skinny, "y = x W^T (+ b) for at most 16 rows of x on the MFMA weight-streaming kernel (batched decode)",
           py::arg("x"), py::arg("W"), py::arg("bias") = py::none());

@@ -33,6 +33,19 @@
 //    before rstd, the bias and the epilogue: a power of two, so the result is the dot product with the dequantised
 //    bf16 weights up to the order of the fp32 sums.  SwiGLU: rows n and F + n each take their own scale.
 // FP8 weights take bf16 activations only, and the one-launch RoPE step (EPI_ROPE) has no FP8 form.
+//
+// MXFP4 weights (MXFP4W):  OCP e2m1 codes, two per byte (even k in the low nibble), in blocks of 32 consecutive k of a
+// row with one e8m0 scale byte b per block, value 2^(b - 127) (scaling_amd/ops/quant.py): 0.53125 bytes per weight.
+// The same kernel, forms, epilogues and rounding points, with a streaming loop of its own (gemv_rows_w4); the format
+// changes
+//  * the piece: 16 bytes per lane are 32 weights = exactly ONE block: K % 32 == 0, four 16-byte loads of x (and of
+//    gamma / add) per piece and input row; the block's scale byte is loaded with the piece and becomes the float
+//    with the bits b << 23 (the quantiser never makes b = 0 or 255);
+//  * the decoding: 8-weight sub-steps, one dword of codes each (never 32 floats per weight row), two codes per
+//    v_cvt_scalef32_pk_f32_fp4 with the block scale applied by the instruction, so code * scale -- exactly the
+//    dequantised bf16 weight -- enters the fp32 FMA and nothing is left to scale after the reduction;
+//  * the launch rules, which are the format's own (w4_rules): at 4 bits a row is a quarter of the pieces.
+// bf16 activations only, no EPI_ROPE form.
 #include "common.h"
 #include "launch.h"
 
@@ -47,14 +60,16 @@ enum { EPI_NONE = 0, EPI_RES = 1, EPI_SWIGLU = 2, EPI_ROPE = 3 };
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // Weight formats: T the element type of W's pointer arithmetic (ldw counts T's), P = 1 << kLog2P weights per 16-byte
-// piece, S one piece as it is held across a trip (ld) until piece() turns it into P floats (unpack).
+// piece, S one piece as it is held across a trip (ld) until piece() turns it into P floats (unpack); ST the type of
+// the scales: one fp32 per row (kScaled) or one byte per piece (kBlock, which has its own streaming loop below).
 // Weights of the activation type E: converted to float at load time (staging them raw reschedules the whole kernel).
 template <typename E>
 struct DenseW {
     typedef E T;
     typedef float S[8];
     static constexpr int kLog2P = 3, P = 8;
-    static constexpr bool kScaled = false;
+    static constexpr bool kScaled = false, kBlock = false;
+    typedef float ST;
     __device__ static __forceinline__ void ld(const E* p, S& s) { V8<E>::ld(p, s); }
     __device__ static __forceinline__ void unpack(const S& s, float (&v)[8]) {
 #pragma unroll
@@ -66,7 +81,8 @@ struct E4M3W {
     typedef uint8_t T;
     typedef u32x4 S;
     static constexpr int kLog2P = 4, P = 16;
-    static constexpr bool kScaled = true;
+    static constexpr bool kScaled = true, kBlock = false;
+    typedef float ST;
     __device__ static __forceinline__ void ld(const uint8_t* p, S& s) { s = *reinterpret_cast<const u32x4*>(p); }
     __device__ static __forceinline__ void unpack(const S& r, float (&v)[16]) {
 #pragma unroll
@@ -78,6 +94,30 @@ struct E4M3W {
             v[4 * i + 2] = hi[0];
             v[4 * i + 3] = hi[1];
         }
+    }
+};
+
+// e2m1 codes, 32 per piece = one MX block with its e8m0 scale byte (kBlock): sub-step h is dword h, 8 codes -> 8 scaled
+// floats in memory order (the low nibble of a byte is the even k)
+struct MXFP4W {
+    typedef uint8_t T;
+    struct S {
+        u32x4 c;
+        float s;
+    };
+    typedef uint8_t ST;
+    static constexpr int kLog2P = 5, P = 32, SUB = 4;
+    static constexpr bool kScaled = false, kBlock = true;
+    __device__ static __forceinline__ void ld(const uint8_t* w, const uint8_t* sc, int g, S& s) {
+        s.c = *reinterpret_cast<const u32x4*>(w + 16 * g);
+        s.s = __uint_as_float((uint32_t)sc[g] << 23);
+    }
+    __device__ static __forceinline__ void unpack(const S& r, int h, float (&v)[8]) {
+        const f32x2 a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(r.c[h], r.s, 0);
+        const f32x2 b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(r.c[h], r.s, 1);
+        const f32x2 c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(r.c[h], r.s, 2);
+        const f32x2 d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(r.c[h], r.s, 3);
+        v[0] = a[0], v[1] = a[1], v[2] = b[0], v[3] = b[1], v[4] = c[0], v[5] = c[1], v[6] = d[0], v[7] = d[1];
     }
 };
 
@@ -198,6 +238,89 @@ __device__ __forceinline__ void gemv_rows(const E* __restrict__ x, int64_t ldx, 
     }
 }
 
+// The same loop for the block-scaled format F (MXFP4W): pieces are F::P = 32 weights with their scale byte (sp: the
+// rows' scale bytes, one per piece), decoded and multiplied in F::SUB sub-steps of P = 8 weights.  A loop of its own,
+// so that the dense and FP8 instantiations keep the code they had.
+// Streams this wave's share of K -- pieces g0, g0 + GS, ... (GS = 64 x waves per row) -- of NR weight rows against
+// all M inputs; returns the wave-reduced (unscaled) dot products acc and (NORM) sums of squares ss.
+template <int M, int NR, typename E, typename F, bool NORM>
+__device__ __forceinline__ void gemv_rows_w4(const E* __restrict__ x, int64_t ldx, const typename F::T* const (&w)[NR],
+                                          const typename F::ST* const (&sp)[NR], int K, int g0, int GS, float (&acc)[NR][M], float (&ss)[M],
+                                          const NormArgs<E>& na, bool write_sum) {
+    constexpr int P = F::P / F::SUB;  // weights per decoding sub-step
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+        for (int m = 0; m < M; ++m) acc[r][m] = 0.f;
+#pragma unroll
+    for (int m = 0; m < M; ++m) ss[m] = 0.f;
+    // one piece p (F::SUB sub-steps of P elements) of every input row against the staged weight pieces ws (NR rows)
+    auto piece = [&](int p, const typename F::S (&ws)[NR]) {
+#pragma unroll
+        for (int h = 0; h < F::SUB; ++h) {
+            const int64_t k0 = (int64_t)F::P * p + P * h;
+            float wv[NR][P];
+#pragma unroll
+            for (int r = 0; r < NR; ++r) F::unpack(ws[r], h, wv[r]);
+            float gv[P];
+            if constexpr (NORM) ld_piece<P>(na.g + k0, gv);
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                float xv[P];
+                ld_piece<P>(x + m * ldx + k0, xv);
+                if constexpr (NORM) {
+                    if (na.add != nullptr) {
+                        float av[P];
+                        ld_piece<P>(na.add + (int64_t)m * K + k0, av);
+#pragma unroll
+                        for (int i = 0; i < P; ++i) xv[i] = rnd<E>(xv[i] + av[i]);
+                        if (write_sum) st_piece<P>(na.sum + (int64_t)m * K + k0, xv);
+                    }
+#pragma unroll
+                    for (int i = 0; i < P; ++i) {
+                        ss[m] = __builtin_fmaf(xv[i], xv[i], ss[m]);
+                        xv[i] *= gv[i];
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < NR; ++r)
+#pragma unroll
+                    for (int i = 0; i < P; ++i) acc[r][m] = __builtin_fmaf(wv[r][i], xv[i], acc[r][m]);
+            }
+        }
+    };
+    constexpr int U = 4 / NR > 0 ? 4 / NR : 1;  // pieces per weight row per trip (4 KiB per wave)
+    const int G = K >> F::kLog2P;                // P-element pieces per row
+    int g = g0;
+    for (; g + GS * (U - 1) < G; g += GS * U) {
+        typename F::S ws[U][NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+#pragma unroll
+            for (int u = 0; u < U; ++u) F::ld(w[r], sp[r], g + GS * u, ws[u][r]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) piece(g + GS * u, ws[u]);
+    }
+    if (g < G) {  // the ragged tail as ONE predicated trip
+        typename F::S ws[U][NR];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (g + GS * u < G) {
+#pragma unroll
+                for (int r = 0; r < NR; ++r) F::ld(w[r], sp[r], g + GS * u, ws[u][r]);
+            }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (g + GS * u < G) piece(g + GS * u, ws[u]);
+    }
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        if constexpr (NORM) ss[m] = wave_sum(ss[m]);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) acc[r][m] = wave_sum(acc[r][m]);
+    }
+}
+
 // lane m < M picks input m's value out of the per-input accumulators (all lanes hold every sum after wave_sum)
 template <int M>
 __device__ __forceinline__ float pick(const float (&a)[M], int lane) {
@@ -213,14 +336,15 @@ __device__ __forceinline__ float pick(const float (&a)[M], int lane) {
 // KS waves per row (1 or 4): with few output rows (N = 4096: o / down projections) one wave per row leaves the CUs
 // a quarter occupied, so the workgroup's four waves split K (interleaved 1 KiB slices, the workgroup streams
 // contiguous 4 KiB) and reduce through LDS in a fixed order.
-// F the weight format: W rows are ldw F::T's apart (elements, or bytes for FP8); scale is read when F::kScaled.
+// F the weight format: W rows are ldw F::T's apart (elements, or bytes of codes); scale is one fp32 per row when
+// F::kScaled, one byte per 32-k block in contiguous rows of K / 32 when F::kBlock, and not read otherwise.
 template <int M, int EPI, typename E, typename F, bool NORM, int RPW, int KS>
 __global__ __launch_bounds__(256) void gemv_kernel(const E* __restrict__ x, int64_t ldx,
                                                    const typename F::T* __restrict__ W, int64_t ldw,
-                                                   const float* __restrict__ scale, const E* __restrict__ bias,
+                                                   const typename F::ST* __restrict__ scale, const E* __restrict__ bias,
                                                    const E* __restrict__ res, int64_t ldr, E* __restrict__ y,
                                                    int64_t ldy, int N, int K, NormArgs<E> na) {
-    static_assert(!F::kScaled || EPI != EPI_ROPE, "EPI_ROPE has no FP8 form");
+    static_assert(!(F::kScaled || F::kBlock) || EPI != EPI_ROPE, "EPI_ROPE has no FP8 / MXFP4 form");
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int row = (blockIdx.x * (4 / KS) + wv / KS) * RPW;
     const int kw = wv % KS;  // this wave's K slice
@@ -237,7 +361,14 @@ __global__ __launch_bounds__(256) void gemv_kernel(const E* __restrict__ x, int6
 #pragma unroll
     for (int r = 0; r < NR; ++r) w[r] = W + (int64_t)wrow[r] * ldw;
     float acc[NR][M], ss[M];
-    gemv_rows<M, NR, E, F, NORM>(x, ldx, w, K, lane + 64 * kw, 64 * KS, acc, ss, na, NORM && row == 0);  // row 0's waves write s
+    if constexpr (F::kBlock) {
+        const typename F::ST* sp[NR];  // the rows' block scales: K / 32 bytes per row, contiguous
+#pragma unroll
+        for (int r = 0; r < NR; ++r) sp[r] = scale + (int64_t)wrow[r] * (K >> 5);
+        gemv_rows_w4<M, NR, E, F, NORM>(x, ldx, w, sp, K, lane + 64 * kw, 64 * KS, acc, ss, na, NORM && row == 0);
+    } else {
+        gemv_rows<M, NR, E, F, NORM>(x, ldx, w, K, lane + 64 * kw, 64 * KS, acc, ss, na, NORM && row == 0);  // row 0's waves write s
+    }
     if constexpr (KS > 1) {
         // partial sums of the K slices: waves 1..KS-1 -> LDS, wave 0 adds them in slice order
         __shared__ float red[KS][NR + 1][M];
@@ -339,7 +470,7 @@ struct Args {
     int64_t ldx;
     const typename F::T* W;
     int64_t ldw;
-    const float* scale;
+    const typename F::ST* scale;
     const E* b;
     const E* r;
     int64_t ldr;
@@ -377,9 +508,54 @@ void launch_r(const Args<E, F>& a) {
     else launch_k<EPI, NORM, RPW, 1>(a);
 }
 
+// MXFP4 launch rules, from N, K and the form: {output rows per wave, waves per row}.  A 4-bit row is a quarter of the
+// 16-byte pieces of its bf16 form (K = 4096: 128, two per lane of ONE wave), so the dense rules' four waves per row
+// leave lanes without a piece, and the weight stream is so short that every wave's own pass over x (and gamma / add)
+// weighs as much as its weights.  Measured on the five 7B shapes at one row, cold cache, every candidate of
+// {1, 2, 4, 8} rows x {1, 4} waves (tools/gemv_bench.py W4_RULES=1, profiles/gemv_w4_rules.log):
+//  * waves per row: 4 only for long rows over few outputs (the plain / residual forms with N <= 8192 and K >= 2 N:
+//    down 10.0 us against 13.2), 1 everywhere else (q/k/v + norm 9.8 us against 15.3, gate/up + norm + SwiGLU 19.3
+//    against 24.7, head 18.5 against 20.8);
+//  * rows per wave: 4 once that still leaves 2048 waves (N x waves per row >= 8192: q/k/v 9.8 us against 15.3 with
+//    two rows, gate/up 19.3 against 22.6, down 10.0 against 11.7, head 18.5 against 19.4), else 2 (o: 5.3 us against
+//    6.6 with four), 1 for odd N.  Eight rows per wave never won (9.9 / 10.7 / 19.4 / 12.9 / 19.4 us) and are not built.
+// The norm / SwiGLU forms were measured at K = 4096 only; they keep one wave per row for every K.
+// The rules were chosen at M = 1 and do not depend on M.  At M = 3 and 4 some of the kernels they select exceed the
+// register file and spill to scratch (the norm + SwiGLU form at four rows per wave: 44-72 VGPRs, 272-400 bytes; the
+// plain SwiGLU form at four rows per wave: 112-144 bytes; the norm form at one row per wave and M = 3): correct, and
+// slow, like every 4-row GEMV here -- 3 and more rows are the skinny kernel's (SKINNY_MIN_ROWS).
+struct W4Rule {
+    int rpw, ks;
+};
+W4Rule g_w4_override{0, 0};  // tools only (sa_launch::gemv_w4_rule): 0 = the rules below
+W4Rule w4_rules(int N, int K, bool swiglu, bool norm) {
+    W4Rule r;
+    r.ks = (!norm && !swiglu && N <= 8192 && K >= 2 * (int64_t)N) ? 4 : 1;
+    r.rpw = (int64_t)N * r.ks >= 8192 ? 4 : 2;
+    if (g_w4_override.rpw > 0) r = g_w4_override;
+    while (N % r.rpw != 0) r.rpw >>= 1;  // rpw divides N
+    return r;
+}
+
+template <int EPI, bool NORM, int RPW, typename E, typename F>
+void launch_w4_k(const Args<E, F>& a, int ks) {
+    if (ks == 4) launch_k<EPI, NORM, RPW, 4>(a);
+    else launch_k<EPI, NORM, RPW, 1>(a);
+}
+
+template <int EPI, bool NORM, typename E, typename F>
+void launch_w4(const Args<E, F>& a) {
+    const W4Rule r = w4_rules(a.N, a.K, EPI == EPI_SWIGLU, NORM);
+    if (r.rpw == 4) launch_w4_k<EPI, NORM, 4>(a, r.ks);
+    else if (r.rpw == 2) launch_w4_k<EPI, NORM, 2>(a, r.ks);
+    else launch_w4_k<EPI, NORM, 1>(a, r.ks);
+}
+
 template <int EPI, bool NORM, typename E, typename F>
 void launch(const Args<E, F>& a) {
-    if constexpr (EPI == EPI_ROPE) {
+    if constexpr (F::kBlock) {
+        launch_w4<EPI, NORM>(a);
+    } else if constexpr (EPI == EPI_ROPE) {
         if constexpr (NORM) launch_r<EPI, NORM, 2>(a);
     } else if (rows_per_wave(NORM, a.N) == 2) {
         launch_r<EPI, NORM, 2>(a);
@@ -395,14 +571,14 @@ void launch_n(const Args<E, F>& a) {
 }
 
 template <typename E, typename F>
-void launch_epi(int epi, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale,
+void launch_epi(int epi, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const typename F::ST* scale,
                 const void* b, const void* r, int64_t ldr, void* y, int64_t ldy, int N, int K, hipStream_t st,
                 const void* norm_w, const void* norm_add, void* norm_sum, float eps, const GemvRope& rp) {
     const Args<E, F> a{M, (const E*)x, ldx, (const typename F::T*)W, ldw, scale, (const E*)b, (const E*)r, ldr, (E*)y,
                        ldy, N, K, st,
                        NormArgs<E>{(const E*)norm_w, (const E*)norm_add, (E*)norm_sum, eps, rp.cosb, rp.sinb, rp.pos,
                                    (E*)rp.q_out, (E*)rp.kc, (E*)rp.vc, rp.nq, rp.nkv, rp.hd, rp.rd, rp.lim, rp.err}};
-    if constexpr (!F::kScaled) {
+    if constexpr (!F::kScaled && !F::kBlock) {
         if (epi == EPI_ROPE) return launch_n<EPI_ROPE>(a);
     }
     if (epi == EPI_SWIGLU) launch_n<EPI_SWIGLU>(a);
@@ -419,16 +595,21 @@ namespace sa_launch {
 // (norm_add / norm_sum [M, K] contiguous; norm_sum receives x + norm_add).
 // scale != nullptr: W holds e4m3fn codes with rows ldw bytes apart and scale one fp32 per code row ([N], [2N] for
 // epi 2); x, b, res, y, norm_* are bf16 whatever dtype says.
+// bscale != nullptr: W holds e2m1 codes, two per byte (rows ldw bytes apart), and bscale one e8m0 byte per 32 k in
+// contiguous rows of K / 32 ([N, K / 32], [2N, K / 32] for epi 2); K % 32 == 0, bf16 as above, epi 0 / 1 / 2.
 void gemv(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale, const void* b,
           void* y, int64_t ldy, int N, int K, hipStream_t st, int epi, const void* res, int64_t ldr, const void* norm_w,
-          const void* norm_add, void* norm_sum, float eps, const GemvRope* rope) {
+          const void* norm_add, void* norm_sum, float eps, const GemvRope* rope, const uint8_t* bscale) {
     const GemvRope z{};
     const GemvRope& rp = rope ? *rope : z;
-    if (scale != nullptr)
+    if (bscale != nullptr)
+        launch_epi<u16, MXFP4W>(epi, M, x, ldx, W, ldw, bscale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps, rp);
+    else if (scale != nullptr)
         launch_epi<u16, E4M3W>(epi, M, x, ldx, W, ldw, scale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps, rp);
     else if (dtype == DT_F16)
         launch_epi<_Float16, DenseW<_Float16>>(epi, M, x, ldx, W, ldw, scale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps, rp);
     else
         launch_epi<u16, DenseW<u16>>(epi, M, x, ldx, W, ldw, scale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps, rp);
 }
+void gemv_w4_rule(int rpw, int ks) { g_w4_override = W4Rule{rpw, ks}; }
 }  // namespace sa_launch

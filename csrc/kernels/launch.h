@@ -193,12 +193,18 @@ namespace sa_launch {
 void gemv(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale, const void* b,
           void* y, int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
           const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
-          const struct GemvRope* rope = nullptr);
+          const struct GemvRope* rope = nullptr, const uint8_t* bscale = nullptr);
+// bscale != nullptr (gemv and skinny): MXFP4 weights -- W points at e2m1 codes, two per byte, rows ldw bytes apart;
+// bscale at one e8m0 byte per 32 k, contiguous rows of K / 32 --, x / b / res / y / norm_* bf16, K % 32 == 0, epi 0 / 1 / 2.
+// gemv_w4_rule: an A/B switch of tools/gemv_bench.py -- forces {rows per wave, waves per row} of the MXFP4 GEMV
+// (0, 0: the kernel's own rules).
+void gemv_w4_rule(int rpw, int ks);
 // skinny.hip: the same layer for M <= 16 rows on the matrix cores (16x16x32 MFMA, weight tile as A, x as B); the
 // arguments, weight formats and epilogues of gemv (epi 0 / 1 / 2, the NORM prologue; no RoPE form).  The launch rules
 // depend on N, K, the format and the form, never on M: row m of y is bitwise the same for every M and whatever the
 // other rows hold.  Rows >= M of x / norm_add / res are never read.
 void skinny(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale, const void* b,
             void* y, int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
-            const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f);
+            const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
+            const uint8_t* bscale = nullptr);
 }  // namespace sa_launch

@@ -42,6 +42,12 @@
 // and feed the bf16 MFMA.  A 16-byte piece is 16 codes = two MFMAs of that lane's k (codes 0..7, 8..15 against
 // x[16 p + 0..7], x[16 p + 8..15]).  The row's power-of-two scale multiplies the fp32 result once, after the
 // reduction and before rstd / bias / epilogue; SwiGLU rows n and F + n keep their own scales.
+//
+// MXFP4 weights (MXFP4W, e2m1 codes in blocks of 32 k with one e8m0 scale byte; ops/quant.py): a lane's 16-byte load is
+// 32 codes of one weight row = exactly one block, and four MFMAs of that lane's k (H = 4): codes 8 hh .. 8 hh + 7 are
+// decoded to bf16 WITH the block scale by v_cvt_scalef32_pk_bf16_fp4 (exact: a code has 2 significant bits, the scale
+// is a power of two) and meet x[32 p + 8 hh ..].  The scale byte is loaded with the piece (same clamped row and
+// piece); nothing is scaled after the reduction.  Four x fragments per step: the per-trip budget shrinks to a quarter.
 #include "common.h"
 #include "launch.h"
 
@@ -98,15 +104,17 @@ template <typename E>
 struct DenseW {
     typedef E T;
     static constexpr int P = 8, H = 1;
-    static constexpr bool kScaled = false;
-    __device__ static __forceinline__ u32x4 frag(const u32x4& w, int) { return w; }
+    static constexpr bool kScaled = false, kBlock = false;
+    typedef float ST;
+    __device__ static __forceinline__ u32x4 frag(const u32x4& w, int, float) { return w; }
 };
 struct E4M3W {
     typedef uint8_t T;
     static constexpr int P = 16, H = 2;
-    static constexpr bool kScaled = true;
+    static constexpr bool kScaled = true, kBlock = false;
+    typedef float ST;
     // eight codes -> eight bf16 in memory order (e4m3x4_to_bf16, common.h)
-    __device__ static __forceinline__ u32x4 frag(const u32x4& w, int hh) {
+    __device__ static __forceinline__ u32x4 frag(const u32x4& w, int hh, float) {
         u32x4 r;
         uint32_t a, b;
         e4m3x4_to_bf16(w[2 * hh], a, b);
@@ -115,6 +123,24 @@ struct E4M3W {
         e4m3x4_to_bf16(w[2 * hh + 1], a, b);
         r[2] = a;
         r[3] = b;
+        return r;
+    }
+};
+
+// e2m1 codes, P = 32 per piece = one MX block (kBlock: ST one e8m0 byte per piece, rows of K / 32 contiguous)
+struct MXFP4W {
+    typedef uint8_t T;
+    typedef uint8_t ST;
+    static constexpr int P = 32, H = 4;
+    static constexpr bool kScaled = false, kBlock = true;
+    // dword hh = eight codes -> eight bf16 (code * block scale) in memory order: the low nibble of a byte is the even k
+    __device__ static __forceinline__ u32x4 frag(const u32x4& w, int hh, float sc) {
+        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+        u32x4 r;
+        r[0] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[hh], sc, 0));
+        r[1] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[hh], sc, 1));
+        r[2] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[hh], sc, 2));
+        r[3] = __builtin_bit_cast(uint32_t, (bf16x2)__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w[hh], sc, 3));
         return r;
     }
 };
@@ -136,10 +162,12 @@ struct NormArgs {
     float eps;
 };
 
-// one trip of a wave: U 32-k (dense) / 64-k (FP8) steps of NT weight tiles, and the x (add, gamma) pieces they meet
-template <int NT, int U, int H, bool NORM>
+// one trip of a wave: U 32-k (dense) / 64-k (FP8) / 128-k (MXFP4) steps of NT weight tiles, and the x (add, gamma)
+// pieces they meet; BS: the block scales of the weight pieces as floats
+template <int NT, int U, int H, bool NORM, bool BS>
 struct Trip {
     u32x4 w[NT][U];
+    float s[BS ? NT : 1][BS ? U : 1];
     u32x4 x[U][H];
     u32x4 a[NORM ? U : 1][H];
     u32x4 g[NORM ? U : 1][H];
@@ -149,15 +177,16 @@ struct Trip {
 template <typename E, typename F, int EPI, bool NORM, int KS, int TPW>
 __global__ __launch_bounds__(256) void skinny_kernel(int M, const E* __restrict__ x, int64_t ldx,
                                                      const typename F::T* __restrict__ W, int64_t ldw,
-                                                     const float* __restrict__ scale, const E* __restrict__ bias,
+                                                     const typename F::ST* __restrict__ scale, const E* __restrict__ bias,
                                                      const E* __restrict__ res, int64_t ldr, E* __restrict__ y,
                                                      int64_t ldy, int N, int K, NormArgs<E> na) {
     constexpr int NS = EPI == EPI_SWIGLU ? 2 : 1;  // weight tiles per output tile
     constexpr int NT = NS * TPW;                   // weight tiles per wave
     constexpr int P = F::P, H = F::H;
     // steps per trip: NT U weight loads per lane and buffer, two buffers (8 - 16 KiB per wave in flight for the plain
-    // dense forms); halved where a step also holds add / gamma (NORM) or two x fragments (FP8), to stay in registers
-    constexpr int BUD = 8 >> ((NORM ? 1 : 0) + (H == 2 ? 1 : 0));
+    // dense forms); halved where a step also holds add / gamma (NORM) or two x fragments (FP8), and again for the four
+    // x fragments of MXFP4, to stay in registers
+    constexpr int BUD = 8 >> ((NORM ? 1 : 0) + (H == 2 ? 1 : 0) + (H == 4 ? 2 : 0));
     constexpr int U = BUD / NT > 4 ? 4 : (BUD / NT < 1 ? 1 : BUD / NT);
     static_assert(NT <= 8 && (KS == 1 || KS == 4), "tiles per wave / K split");
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -170,11 +199,15 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, const E* __restrict_
 
     // weight rows of this lane, clamped into [0, N): a clamped row's accumulators are never stored
     const typename F::T* wp[NT];
+    const typename F::ST* sp[NT];  // kBlock: the rows' block scales, one byte per piece
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
         const int n = min((tile0 + j) * 16 + c, N - 1);
 #pragma unroll
-        for (int s = 0; s < NS; ++s) wp[s * TPW + j] = W + ((int64_t)n + (int64_t)s * N) * ldw;
+        for (int s = 0; s < NS; ++s) {
+            wp[s * TPW + j] = W + ((int64_t)n + (int64_t)s * N) * ldw;
+            sp[s * TPW + j] = F::kBlock ? scale + ((int64_t)n + (int64_t)s * N) * G : nullptr;
+        }
     }
     const E* xr = x + (int64_t)c * ldx;                       // dereferenced only when row_ok
     const bool has_add = NORM && na.add != nullptr;
@@ -186,7 +219,7 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, const E* __restrict_
     for (int j = 0; j < NT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float ss = 0.f;
 
-    typedef Trip<NT, U, H, NORM> TripT;
+    typedef Trip<NT, U, H, NORM, F::kBlock> TripT;
     // this lane's piece of step u of trip t
     auto piece = [&](int t, int u) { return (t * KS + kw) * (4 * U) + 4 * u + h; };
     auto load = [&](TripT& tr, int t) {
@@ -195,7 +228,10 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, const E* __restrict_
             const int p = piece(t, u);
             const int pc = min(p, G - 1);  // clamped: the same row's last piece, met by a zero x fragment
 #pragma unroll
-            for (int j = 0; j < NT; ++j) tr.w[j][u] = ld_w(wp[j] + (int64_t)pc * P);
+            for (int j = 0; j < NT; ++j) {
+                tr.w[j][u] = ld_w(wp[j] + (int64_t)pc * (16 / (int)sizeof(typename F::T)));
+                if constexpr (F::kBlock) tr.s[j][u] = __uint_as_float((uint32_t)sp[j][pc] << 23);
+            }
             const bool ok = row_ok && p < G;
 #pragma unroll
             for (int hh = 0; hh < H; ++hh) {
@@ -236,7 +272,8 @@ __global__ __launch_bounds__(256) void skinny_kernel(int M, const E* __restrict_
                     b = Act<E>::pack(xv);  // rnd(s * gamma)
                 }
 #pragma unroll
-                for (int j = 0; j < NT; ++j) acc[j] = Act<E>::mma(F::frag(tr.w[j][u], hh), b, acc[j]);
+                for (int j = 0; j < NT; ++j)
+                    acc[j] = Act<E>::mma(F::frag(tr.w[j][u], hh, F::kBlock ? tr.s[j][u] : 0.f), b, acc[j]);
             }
         }
     };
@@ -311,7 +348,7 @@ struct Args {
     int64_t ldx;
     const typename F::T* W;
     int64_t ldw;
-    const float* scale;
+    const typename F::ST* scale;
     const E* b;
     const E* r;
     int64_t ldr;
@@ -356,7 +393,7 @@ void launch(const Args<E, F>& a) {
 }
 
 template <typename E, typename F>
-void launch_epi(int epi, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale,
+void launch_epi(int epi, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const typename F::ST* scale,
                 const void* b, const void* r, int64_t ldr, void* y, int64_t ldy, int N, int K, hipStream_t st,
                 const void* norm_w, const void* norm_add, void* norm_sum, float eps) {
     const Args<E, F> a{M, (const E*)x, ldx, (const typename F::T*)W, ldw, scale, (const E*)b, (const E*)r, ldr, (E*)y,
@@ -379,11 +416,15 @@ namespace sa_launch {
 // epi 0: y = x W^T (+ b); 1: y = rnd(x W^T (+ b)) + res; 2: SwiGLU over W = [gate; up] (N = F output columns).
 // norm_w != nullptr (epi 0 / 2): x is first replaced by rms_norm(x (+ norm_add), norm_w, eps) inside the same pass.
 // scale != nullptr: W holds e4m3fn codes (rows ldw bytes apart), x / b / res / y / norm_* are bf16 whatever dtype says.
+// bscale != nullptr: W holds e2m1 codes, two per byte, bscale one e8m0 byte per 32 k ([N, K / 32] contiguous; launch.h).
 void skinny(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale, const void* b,
             void* y, int64_t ldy, int N, int K, hipStream_t st, int epi, const void* res, int64_t ldr, const void* norm_w,
-            const void* norm_add, void* norm_sum, float eps) {
+            const void* norm_add, void* norm_sum, float eps, const uint8_t* bscale) {
     if (M < 1 || M > 16 || N < 1 || K < 8) return;  // (the bindings reject these; never launch on them)
-    if (scale != nullptr)
+    if (bscale != nullptr) {
+        if (K % 32 != 0) return;
+        launch_epi<u16, MXFP4W>(epi, M, x, ldx, W, ldw, bscale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps);
+    } else if (scale != nullptr)
         launch_epi<u16, E4M3W>(epi, M, x, ldx, W, ldw, scale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps);
     else if (dtype == DT_F16)
         launch_epi<_Float16, DenseW<_Float16>>(epi, M, x, ldx, W, ldw, scale, b, res, ldr, y, ldy, N, K, st, norm_w, norm_add, norm_sum, eps);

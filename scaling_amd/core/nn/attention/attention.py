@@ -30,7 +30,7 @@ from ..linear import ColumnParallelLinear, RowParallelLinear
 from ..linear.fused import fused_column_linear
 from ..linear.tp_overlap import sp_gather_column
 from ..linear.utils import all_concat, all_reduce_scatter_to_sequence_parallel, all_shard
-from ..linear.main_grad import adjacent_w8, adjacent_weights, invalidate_transposed_weights
+from ..linear.main_grad import adjacent_weights, adjacent_wq, invalidate_transposed_weights
 from ..lora import ParallelLoRa
 from ..lora_config import LoRaConfig, LoRAModuleType
 from ..masked_softmax import MaskedSoftmax, MaskedSoftmaxConfig, MaskedSoftmaxKernel
@@ -896,11 +896,11 @@ class ParallelSelfAttention(torch.nn.Module):
         x2 = x.reshape(rows, K)
         if w is None or not decode_kernel(rows, "_norm_ok")(x2, w, nw[0]):
             return None
-        w8 = adjacent_w8(weights)
-        if w8 is not None and decode_kernel(rows, "_w8_norm_ok")(x2, w8[0], w8[1], nw[0]):
-            # quantised weights (ops/quant.py): the FP8 GEMV with the norm folded in; the one-launch RoPE step has no
-            # FP8 form, so RoPE + K/V append follow as their own launch (_decode_rope_append)
-            _, base = decode_kernel(rows, "_w8_norm")(x2, None, nw[0], nw[1], w8[0], w8[1], 0)
+        wq = adjacent_wq(weights)  # (suffix, copy, scales) of either quantised format
+        if wq is not None and decode_kernel(rows, wq[0] + "_norm_ok")(x2, wq[1], wq[2], nw[0]):
+            # quantised weights (ops/quant.py): the format's GEMV with the norm folded in; the one-launch RoPE step has
+            # no FP8 or MXFP4 form, so RoPE + K/V append follow as their own launch (_decode_rope_append)
+            _, base = decode_kernel(rows, wq[0] + "_norm")(x2, None, nw[0], nw[1], wq[1], wq[2], 0)
             return {"projected_base": base.view(*x.shape[:-1], w.shape[0])}
         step = self._decode_norm_rope_step(x2, nw, w, position_ids, use_cache, reset_cache, cache_index)
         if step is not None:

@@ -53,6 +53,7 @@ from ....ops.attention import stash_gemm
 from ....ops.gemm import linear as gemm_linear
 from ....ops.gemm import decode_rows_limit, mm, mm_nt, transpose2d, wgrad
 from ....ops.quant import adjacent_w8 as _adjacent_w8
+from ....ops.quant import adjacent_wq as _adjacent_wq
 from ...utils.debug_env import side_streams_enabled
 
 _GEN = [0]
@@ -180,6 +181,13 @@ def adjacent_w8(weights: Sequence[torch.Tensor]) -> Optional[tuple[torch.Tensor,
     return _adjacent_w8(weights)
 
 
+def adjacent_wq(weights: Sequence[torch.Tensor]) -> Optional[tuple[str, torch.Tensor, torch.Tensor]]:
+    """The fused quantised copy of weights quantised as one group, whichever format it has: ``(suffix, copy,
+    scales)`` with the suffix of the bindings that take it (``"_w8"`` / ``"_w4"``; ``ops/quant.py``); None without a
+    valid copy of every member (a stale copy is dropped there, with a warning)."""
+    return _adjacent_wq(weights)
+
+
 def _main_grad_target(weights: Sequence[torch.Tensor]) -> Optional[torch.Tensor]:
     if not all(getattr(w, "_sa_main_grad", False) and w.grad is not None for w in weights):
         return None
@@ -243,10 +251,10 @@ class _MultiLinear(torch.autograd.Function):
         b = None
         if has_bias:
             b = biases[0] if n == 1 else torch.cat(biases, dim=0)  # type: ignore[arg-type]
-        # decode-sized rows of quantised weights stream the FP8 copy (w itself may be a fresh view over the group)
+        # decode-sized rows of quantised weights stream the copy (w itself may be a fresh view over the group)
         K = x.shape[-1]
-        w8 = adjacent_w8(weights) if K and 0 < x.numel() // K <= decode_rows_limit() else None  # type: ignore[arg-type]
-        out = stash_gemm(lambda: gemm_linear(x, w, b, w8=w8))
+        wq = adjacent_wq(weights) if K and 0 < x.numel() // K <= decode_rows_limit() else None  # type: ignore[arg-type]
+        out = stash_gemm(lambda: gemm_linear(x, w, b, wq=wq))
         wt = _transposed(weights, w) if want_wt else None
         ctx.has_wt = wt is not None
         ctx.save_for_backward(x, wt if wt is not None else w, *weights)

@@ -23,7 +23,7 @@ from .activation_function import ActivationFunction, get_activation_function
 from .linear import ColumnParallelLinear, RowParallelLinear
 from .linear.fused import fused_column_linear
 from .linear.tp_overlap import sp_gather_column
-from .linear.main_grad import adjacent_w8, adjacent_weights
+from .linear.main_grad import adjacent_weights, adjacent_wq
 
 
 def _intermediate(io_features: int, factor: float) -> int:
@@ -117,16 +117,17 @@ class ParallelSwiGLUMLP(torch.nn.Module):
             return None
         return w, wo
 
-    def _decode_w8(self) -> tuple[Optional[tuple], Optional[tuple]]:
-        """The valid FP8 copies ``(q, scale)`` of ``[gate; up]`` and of the down projection (``ops/quant.py``), each
-        None without one: that GEMV then streams the bf16 weight as before."""
-        return adjacent_w8([self.dense_in.weight, self.siglu_weight.weight]), adjacent_w8([self.dense_out.weight])
+    def _decode_wq(self) -> tuple[Optional[tuple], Optional[tuple]]:
+        """The valid quantised copies of ``[gate; up]`` and of the down projection (``ops/quant.py``), each as
+        ``(suffix, copy, scales)`` -- ``("_w8", q, scale)`` or ``("_w4", codes, scales)``, the suffix naming the bindings
+        that take the copy -- or None without one: that GEMV then streams the bf16 weight as before."""
+        return adjacent_wq([self.dense_in.weight, self.siglu_weight.weight]), adjacent_wq([self.dense_out.weight])
 
     @staticmethod
-    def _down_residual(a: torch.Tensor, wo: torch.Tensor, wo8: Optional[tuple], res: torch.Tensor) -> torch.Tensor:
+    def _down_residual(a: torch.Tensor, wo: torch.Tensor, woq: Optional[tuple], res: torch.Tensor) -> torch.Tensor:
         rows = a.shape[0]
-        if wo8 is not None and decode_kernel(rows, "_w8_ok")(a, wo8[0], wo8[1]):
-            return decode_kernel(rows, "_w8_residual")(a, wo8[0], wo8[1], res)
+        if woq is not None and decode_kernel(rows, woq[0] + "_ok")(a, woq[1], woq[2]):
+            return decode_kernel(rows, woq[0] + "_residual")(a, woq[1], woq[2], res)
         return decode_kernel(rows, "_residual")(a, wo, res)
 
     def decode_forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> Optional[torch.Tensor]:
@@ -138,12 +139,12 @@ class ParallelSwiGLUMLP(torch.nn.Module):
             return None
         rows = x.numel() // x.shape[-1]
         x2 = x.reshape(rows, -1)
-        w8, wo8 = self._decode_w8()
-        if w8 is not None and decode_kernel(rows, "_w8_ok")(x2, w8[0], w8[1]):
-            h = decode_kernel(rows, "_w8_swiglu")(x2, w8[0], w8[1])
+        wq, woq = self._decode_wq()
+        if wq is not None and decode_kernel(rows, wq[0] + "_ok")(x2, wq[1], wq[2]):
+            h = decode_kernel(rows, wq[0] + "_swiglu")(x2, wq[1], wq[2])
         else:
             h = decode_kernel(rows, "_swiglu")(x2, ws[0])
-        return self._down_residual(h, ws[1], wo8, residual.reshape(rows, -1)).view(residual.shape)
+        return self._down_residual(h, ws[1], woq, residual.reshape(rows, -1)).view(residual.shape)
 
     def decode_forward_norm(self, h: torch.Tensor, residual: torch.Tensor, norm: torch.nn.Module) -> Optional[torch.Tensor]:
         """``s + self(norm(s))`` with ``s = residual + h`` (the post-attention residual add, RMSNorm and MLP of a
@@ -163,12 +164,12 @@ class ParallelSwiGLUMLP(torch.nn.Module):
         h2 = h.reshape(rows, -1)
         if not decode_kernel(rows, "_norm_ok")(h2, ws[0], nw[0]):
             return None
-        w8, wo8 = self._decode_w8()
-        if w8 is not None and decode_kernel(rows, "_w8_norm_ok")(h2, w8[0], w8[1], nw[0]):
-            s, a = decode_kernel(rows, "_w8_norm")(h2, residual.reshape(rows, -1), nw[0], nw[1], w8[0], w8[1], 2)
+        wq, woq = self._decode_wq()
+        if wq is not None and decode_kernel(rows, wq[0] + "_norm_ok")(h2, wq[1], wq[2], nw[0]):
+            s, a = decode_kernel(rows, wq[0] + "_norm")(h2, residual.reshape(rows, -1), nw[0], nw[1], wq[1], wq[2], 2)
         else:
             s, a = decode_kernel(rows, "_norm")(h2, residual.reshape(rows, -1), nw[0], nw[1], ws[0], 2)
-        return self._down_residual(a, ws[1], wo8, s).view(residual.shape)
+        return self._down_residual(a, ws[1], woq, s).view(residual.shape)
 
     def forward(self, x: torch.Tensor, sp_shard: bool = False) -> torch.Tensor:
         """``sp_shard``: ``x`` is this rank's sequence-parallel token shard; its gather runs folded into (and overlapped

@@ -31,7 +31,7 @@ from typing import Callable, Iterator, Optional
 import torch
 
 from ._ext import ext, use_native
-from .quant import w8_of
+from .quant import has_copy, wq_of
 
 
 _WGRAD_RAGGED = os.environ.get("SCALING_AMD_WGRAD_RAGGED", "1") != "0"
@@ -95,7 +95,7 @@ def use_skinny(rows: int) -> bool:
 
 def decode_kernel(rows: int, suffix: str = "") -> Callable:
     """``ext().gemv<suffix>`` or, where ``use_skinny(rows)``, ``ext().skinny<suffix>``: the two kernels bind the same
-    names with the same signatures (``_ok``, ``_residual``, ``_swiglu``, ``_norm``, ``_w8...``)."""
+    names with the same signatures (``_ok``, ``_residual``, ``_swiglu``, ``_norm``, ``_w8...``, ``_w4...``)."""
     return getattr(ext(), ("skinny" if use_skinny(rows) else "gemv") + suffix)
 # products of at most this many multiply-adds go through cached hipBLASLt plans (csrc/blaslt.cpp): torch's path
 # re-plans every call (~25-30 us of host time), which only a host-bound small model notices; 0 disables
@@ -130,25 +130,26 @@ def mm_nt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
-           w8: Optional[tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
+           wq: Optional[tuple[str, torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """``F.linear(x, w, b)``; decode-sized inputs (<= 4 rows) on the GEMV kernel, inside ``skinny_gemm()``
     ``SKINNY_MIN_ROWS`` to 16 rows on the MFMA kernel under the same conditions.
 
     The GEMV kernel is a raw op without autograd, so it only serves calls that build no graph (grad mode off, or
     no operand requiring grad); a tiny training micro-batch through a tied head keeps ``F.linear``'s backward.
 
-    A weight quantised by ``ops.quant`` (``w8``: its valid FP8 copy ``(q, scale)``, looked up on ``w`` when not
-    given) streams the copy through the FP8 GEMV (``csrc/kernels/gemv.hip``) on that same branch; ``w`` holds
-    the dequantised values, so every other branch computes the same function."""
+    A weight quantised by ``ops.quant`` (``wq``: its valid copy with the suffix of the bindings that take it,
+    ``("_w8", q, scale)`` or ``("_w4", codes, scales)``, looked up on ``w`` when not given) streams the copy through
+    that format's kernels (``csrc/kernels/gemv.hip``, ``skinny.hip``) on that
+    same branch; ``w`` holds the dequantised values, so every other branch computes the same function."""
     K = x.shape[-1]
     rows = x.numel() // K if K else 0
     needs_graph = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad))
-    if w8 is None and getattr(w, "_sa_w8", None) is not None:
-        w8 = w8_of(w)  # (drops a stale copy, whichever branch serves this call)
+    if wq is None and has_copy(w):
+        wq = wq_of(w)  # (drops a stale copy, whichever branch serves this call)
     if 0 < rows <= decode_rows_limit() and not needs_graph and use_native(x) and w.dim() == 2:
         x2 = x.reshape(rows, K)
-        if w8 is not None and decode_kernel(rows, "_w8_ok")(x2, w8[0], w8[1]) and (b is None or b.dtype == x.dtype):
-            return decode_kernel(rows, "_w8")(x2, w8[0], w8[1], b).reshape(*x.shape[:-1], w.shape[0])
+        if wq is not None and decode_kernel(rows, wq[0] + "_ok")(x2, wq[1], wq[2]) and (b is None or b.dtype == x.dtype):
+            return decode_kernel(rows, wq[0])(x2, wq[1], wq[2], b).reshape(*x.shape[:-1], w.shape[0])
         if decode_kernel(rows, "_ok")(x2, w) and (b is None or b.dtype == w.dtype):
             return decode_kernel(rows)(x2, w, b).reshape(*x.shape[:-1], w.shape[0])
     if not needs_graph and w.dim() == 2 and _lt_ok(x, w, rows, w.shape[0], K) and (b is None or b.dtype == w.dtype):

@@ -1,7 +1,7 @@
 """Batch-1 decode latency on one GPU: eager cached generation vs HIP-graph-captured decoding, greedy or sampled.
 
     python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64] [--sampler T,K,P | torch:T,K,P]
-                                 [--weights fp8_e4m3 [--lm-head]] [--batch B [--skinny]]
+                                 [--weights fp8_e4m3 | mxfp4 | bf16,fp8_e4m3,mxfp4 [--lm-head]] [--batch B [--skinny]]
                                  [--kv-cache bf16,fp8_e4m3 [--rounds N]] [--paged 0,64] [--continuous N]
 
 ``--batch B`` times batched generation instead (``generate_batch`` / ``BatchDecoder``): B random prompts of lengths
@@ -11,7 +11,10 @@ the graph limit) the captured loop and ``graph_tokens_equal_eager``.  ``--skinny
 
 ``--weights fp8_e4m3`` decodes the model after ``quantize_weights()`` (FP8 weight-only decoding; ``--lm-head`` includes
 the LM head); ``weights_gib`` and ``graph_gb_per_s`` then count what one decode step streams (the FP8 copies in place of
-their bf16 parameters).
+their bf16 parameters).  ``--weights mxfp4`` does the same with the MXFP4 copies (``quantize_weights("mxfp4")``).  A comma
+list such as ``bf16,fp8_e4m3,mxfp4`` measures the formats alternately in this process, ``--rounds`` times, one JSON line
+each: the model is re-quantised in place before each measurement (``bf16`` after a quantised format drops the copies and
+decodes from the parameters, which then hold dequantised values: the same kernels and bytes as a fresh bf16 model).
 
 ``--kv-cache fp8_e4m3`` (with ``--batch``) decodes over the FP8 KV cache (``generate_batch(kv_cache=...)``); a comma
 list such as ``bf16,fp8_e4m3`` measures the settings alternately in this process, ``--rounds`` times, one JSON line
@@ -55,8 +58,9 @@ def main() -> None:
     p.add_argument("--tokens", type=int, default=64)
     p.add_argument("--num-layers", type=int, default=None)
     p.add_argument("--sampler", default=None, help="T,K,P: fused Sampler; torch:T,K,P: torch composition (eager only)")
-    p.add_argument("--weights", default="bf16", choices=["bf16", "fp8_e4m3"], help="fp8_e4m3: quantize_weights() first")
-    p.add_argument("--lm-head", action="store_true", help="with --weights fp8_e4m3: quantise the LM head too")
+    p.add_argument("--weights", default="bf16", help="bf16, fp8_e4m3 or mxfp4 (quantize_weights() first), or a comma list "
+                   "measured alternately in this process, --rounds times")
+    p.add_argument("--lm-head", action="store_true", help="with quantised --weights: quantise the LM head too")
     p.add_argument("--batch", type=int, default=0, help="B >= 1: time batched generation of B prompts")
     p.add_argument("--skinny", action="store_true", help="with --batch: skinny_gemm=True (MFMA kernels, graph up to B = 16)")
     p.add_argument("--kv-cache", default="bf16", help="with --batch: bf16, fp8_e4m3 (generate_batch(kv_cache=...)), or a "
@@ -70,13 +74,15 @@ def main() -> None:
     a = p.parse_args()
     a.page_list = [int(x) or None for x in a.paged.split(",")]
     a.kv_list = [None if k == "bf16" else k for k in a.kv_cache.split(",")]
+    a.weight_list = a.weights.split(",")
+    if any(w not in ("bf16", "fp8_e4m3", "mxfp4") for w in a.weight_list):
+        raise SystemExit("--weights: bf16, fp8_e4m3, mxfp4 or a comma list of them")
     if a.kv_list != [None] and a.batch < 1:
         raise SystemExit("--kv-cache needs --batch (the single-sequence eager loop keeps a growing bf16 cache)")
     from scaling_amd.models import llama_architecture
     from scaling_amd.transformer.context.config import TransformerArchitectureConfig
     from scaling_amd.transformer.inference import (Sampler, TransformerInferenceModule, sample_argmax, sample_temperature,
                                                    top_k_transform, top_p_transform)
-    from scaling_amd.transformer.inference.graph_decode import GraphDecoder
     from scaling_amd.transformer.model.model import get_transformer_layer_specs
     from scaling_amd.utils.gemm_tuning import enable_tuned_gemms
 
@@ -88,9 +94,18 @@ def main() -> None:
     torch.manual_seed(0)
     m = TransformerInferenceModule(get_transformer_layer_specs(arch), devices=(0,))
     prompt = torch.randint(1, arch.vocab_size, (a.prompt,)).tolist()
-    quantised = None
-    if a.weights != "bf16":
-        quantised = m.quantize_weights(a.weights, include_lm_head=a.lm_head)
+
+    def set_weights(scheme):
+        """Puts the model into ``scheme`` (in place) and returns quantize_weights()'s summary, None for bf16."""
+        from scaling_amd.ops import quant
+
+        a.weights = scheme
+        if scheme == "bf16":
+            for prm in m.parameters():
+                quant.drop_w8(prm)
+                quant.drop_w4(prm)
+            return None
+        return m.quantize_weights(scheme, include_lm_head=a.lm_head)
 
     sample_fn, graph_ok, mode = sample_argmax, True, "greedy"
     if a.sampler:
@@ -116,13 +131,24 @@ def main() -> None:
         if not graph_ok:
             raise SystemExit("--batch needs a graph-safe sampler (greedy or T,K,P)")
         for _ in range(a.rounds):
-            for kv in a.kv_list:
-                if a.continuous:
-                    continuous_bench(m, a, arch, sample_fn, timed, kv)
-                    continue
-                for page in a.page_list:
-                    batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv, page)
+            for scheme in a.weight_list:
+                quantised = set_weights(scheme)
+                for kv in a.kv_list:
+                    if a.continuous:
+                        continuous_bench(m, a, arch, sample_fn, timed, kv)
+                        continue
+                    for page in a.page_list:
+                        batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv, page)
         return
+
+    for _ in range(a.rounds):
+        for scheme in a.weight_list:
+            single_bench(m, a, arch, prompt, sample_fn, graph_ok, mode, metric, timed, set_weights(scheme))
+
+
+def single_bench(m, a, arch, prompt, sample_fn, graph_ok, mode, metric, timed, quantised) -> None:
+    """Batch 1: the eager loop and the captured loop in the model's current weight format."""
+    from scaling_amd.transformer.inference.graph_decode import GraphDecoder
 
     m.generate(4, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn)  # warm-up (library handles, tables)
     t1, _ = timed(lambda: m.generate(1, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn))
@@ -130,8 +156,8 @@ def main() -> None:
     eager_ms = 1000.0 * (tn - t1) / a.tokens
     weights = sum(p.numel() * p.element_size() for p in m.parameters())
     extra = {"weights": a.weights}
-    if quantised is not None:  # a decode step streams the FP8 copies in place of their bf16 parameters
-        weights = weights - quantised["bf16_bytes"] + quantised["fp8_bytes"]
+    if quantised is not None:  # a decode step streams the quantised copies in place of their bf16 parameters
+        weights = weights - quantised["bf16_bytes"] + quantised["quantized_bytes"]
         extra.update(lm_head=a.lm_head, quantised_tensors=quantised["tensors"], skipped=len(quantised["skipped"]),
                      bf16_gib_replaced=round(quantised["bf16_bytes"] / 2**30, 2))
     if not graph_ok:
@@ -228,7 +254,7 @@ def batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv=None, page=Non
     eager_ms = 1000.0 * te / steps
     weights = sum(p.numel() * p.element_size() for p in m.parameters())
     if quantised is not None:
-        weights = weights - quantised["bf16_bytes"] + quantised["fp8_bytes"]
+        weights = weights - quantised["bf16_bytes"] + quantised["quantized_bytes"]
     res = {"metric": "batched decode ms/step", "batch": B, "sampler": mode, "model": a.model, "layers": arch.num_layers,
            "prompt": a.prompt, "tokens": steps, "weights": a.weights, "skinny_gemm": a.skinny, "kv_cache": kv or "bf16",
            "page_size": page or 0,

@@ -4,6 +4,8 @@ inputs at the tests' shapes -- M = 1..4, one wave per row and four, full / tail-
 row-strided weight view and a row-strided x: run it under two builds (``SCALING_AMD_EXT_SO``) and diff the printed
 lines to check that a kernel change is bit-identical.  The same for the MFMA kernel's entry points
 (``csrc/kernels/skinny.hip``, ``skinny*`` / ``skinny_w8*``) at M = 1, 5, 16 and one shape per launch rule.
+The MXFP4 entry points (``gemv_w4*`` / ``skinny_w4*``) follow as lines tagged ``w4`` when the build has them, at the
+same shapes with K rounded up to a multiple of 32.
 
 usage: python tools/gemv_bits.py
 """
@@ -126,10 +128,37 @@ def run_skinny(dt, fp8: bool) -> None:
                           f"y {digest(yn)}", flush=True)
 
 
+def run_w4() -> None:
+    e = ext()
+    up = lambda k: -(-k // 32) * 32  # noqa: E731
+    q4 = lambda seed, N, K: quant.quantize_rows_mxfp4(weight(seed, N, K, torch.bfloat16))  # noqa: E731
+    for kind, rows in (("gemv", (1, 2, 3, 4)), ("skinny", (1, 5, 16))):
+        fn = lambda name: getattr(e, kind + "_w4" + name)  # noqa: E731
+        shapes = SHAPES + [(136, 528)] if kind == "gemv" else [(5, 16), (1003, 208), (64, 4112), (263, 528), (136, 528),
+                                                                (8200, 64), (32781, 64)]
+        for N, K in [(n, up(k)) for n, k in shapes]:
+            wa, w2 = q4(N + K, N, K), q4(5 + N + K, 2 * N, K)
+            gam = (1 + 0.1 * randn(3 * K, K, dt=torch.float32)).to(torch.bfloat16)
+            for M in rows:
+                x, add = randn(7 * N + K + M, M, K), randn(2 * (N + K) + M, M, K)
+                b, res = randn(3 * N + 1, N), randn(4 * N + M, M, N)
+                y = [fn("")(xx, *wa, bb) for xx, bb in ((x, None), (x, b), (strided(x, 24, 8), b))]
+                print(f"w4 {kind} N={N} K={K} M={M}: y {digest(y[0])} bias {digest(y[1])} xview {digest(y[2])}", flush=True)
+                print(f"w4 {kind}_residual N={N} K={K} M={M}: y {digest(fn('_residual')(x, *wa, res))}", flush=True)
+                print(f"w4 {kind}_swiglu F={N} K={K} M={M}: y {digest(fn('_swiglu')(x, *w2))}", flush=True)
+                for a in (None, add):
+                    for epi, ww in ((0, wa), (2, w2)):
+                        s, yn = fn("_norm")(x, a, gam, 1e-5, *ww, epi)
+                        print(f"w4 {kind}_norm N={N} K={K} M={M} add={a is not None} epi={epi}: s {digest(s)} "
+                              f"y {digest(yn)}", flush=True)
+
+
 run(torch.bfloat16, fp8=False, rope=True, all_paths=True)
 run(torch.float16, fp8=False, rope=False, all_paths=False)  # the plain and NORM cases
 run(torch.bfloat16, fp8=True, rope=False, all_paths=True)
 run_skinny(torch.bfloat16, fp8=False)
 run_skinny(torch.float16, fp8=False)
 run_skinny(torch.bfloat16, fp8=True)
+if hasattr(ext(), "gemv_w4"):
+    run_w4()
 torch.cuda.synchronize()
