@@ -449,24 +449,27 @@ at::Tensor transpose2d(const at::Tensor& x) {
 //    codes per byte, scales [N, K / 32] uint8 (e8m0), x bf16 [M, K].  16-byte pieces of 32 codes = one block:
 //    K % 32 == 0, code rows exactly K / 2 bytes apart (whole rows of the group's buffer), scale rows contiguous.
 // Each pair of bound functions is one worker; name is the bound function's, for the error messages.
-// The skinny* names are the same layers on the MFMA kernel (skinny.hip): the same operand rules with M <= 16 (skinny
-// = true below), the same signatures and return conventions; there is no RoPE form.
-constexpr int64_t kGemvRows = 4, kSkinnyRows = 16;
+// The skinny* names are the same layers on the MFMA kernel (skinny.hip): the same operand rules with M <= 16 (kern
+// = kSkinny below), the same signatures and return conventions; there is no RoPE form.  The wide* names are the same
+// again on the LDS-shared-x MFMA kernel (wide.hip), M <= 64.
+// kern selects the kernel of the shared workers below and its row limit
+enum { kGemv = 0, kSkinny = 1, kWide = 2 };
+constexpr int64_t kMaxRows[3] = {4, 16, 64};
 // (a 2-D scale tensor marks the MXFP4 format for the shared workers below; the _w8 entry points take 1-D scales only)
 bool is_w4(const at::Tensor* scale) { return scale && scale->dim() == 2; }
-bool gemv_w4_operands_ok(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S, bool skinny) {
+bool gemv_w4_operands_ok(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S, int kern) {
     if (!(x.is_cuda() && C.is_cuda() && S.is_cuda() && x.dim() == 2 && C.dim() == 2 && S.dim() == 2)) return false;
     if (C.device() != x.device() || S.device() != x.device()) return false;
     if (x.scalar_type() != at::kBFloat16 || C.scalar_type() != at::kByte || S.scalar_type() != at::kByte) return false;
     const int64_t K = x.size(1), N = C.size(0);
     if (K < 32 || K % 32 != 0 || N < 1 || C.size(1) != K / 2 || S.size(0) != N || S.size(1) != K / 32) return false;
-    if (x.size(0) < 1 || x.size(0) > (skinny ? kSkinnyRows : kGemvRows)) return false;
+    if (x.size(0) < 1 || x.size(0) > kMaxRows[kern]) return false;
     if (x.stride(1) != 1 || (x.size(0) > 1 && x.stride(0) % 8 != 0)) return false;
     if (C.stride(1) != 1 || C.stride(0) != K / 2 || !S.is_contiguous()) return false;
     return (uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)C.data_ptr() % 16 == 0;
 }
-bool gemv_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale, bool skinny = false) {
-    if (is_w4(scale)) return gemv_w4_operands_ok(x, W, *scale, skinny);
+bool gemv_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale, int kern = kGemv) {
+    if (is_w4(scale)) return gemv_w4_operands_ok(x, W, *scale, kern);
     const int64_t P = scale ? 16 : 8;  // weights per 16-byte piece
     if (!(x.is_cuda() && W.is_cuda() && x.dim() == 2 && W.dim() == 2)) return false;
     if (scale) {
@@ -481,25 +484,33 @@ bool gemv_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor
     } else if (x.scalar_type() != W.scalar_type() || (x.scalar_type() != at::kBFloat16 && x.scalar_type() != at::kHalf)) {
         return false;
     }
-    if (x.size(0) < 1 || x.size(0) > (skinny ? kSkinnyRows : kGemvRows) || x.size(1) != W.size(1) || x.size(1) % P != 0 || W.size(0) < 1) return false;
+    if (x.size(0) < 1 || x.size(0) > kMaxRows[kern] || x.size(1) != W.size(1) || x.size(1) % P != 0 || W.size(0) < 1) return false;
     if (x.stride(1) != 1 || W.stride(1) != 1 || (x.size(0) > 1 && x.stride(0) % 8 != 0) || W.stride(0) % P != 0)
         return false;
     return (uintptr_t)x.data_ptr() % 16 == 0 && (uintptr_t)W.data_ptr() % 16 == 0;
 }
 bool gemv_norm_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale, const at::Tensor& gamma,
-                           bool skinny = false) {
-    if (!gemv_operands_ok(x, W, scale, skinny) || !x.is_contiguous()) return false;
+                           int kern = kGemv) {
+    if (!gemv_operands_ok(x, W, scale, kern) || !x.is_contiguous()) return false;
     return gamma.is_cuda() && gamma.dim() == 1 && gamma.numel() == x.size(1) && gamma.is_contiguous() &&
            gamma.scalar_type() == x.scalar_type() && (uintptr_t)gamma.data_ptr() % 16 == 0;
 }
 const float* scale_ptr(const at::Tensor* scale) { return scale && !is_w4(scale) ? scale->data_ptr<float>() : nullptr; }
 const uint8_t* bscale_ptr(const at::Tensor* scale) { return is_w4(scale) ? scale->data_ptr<uint8_t>() : nullptr; }
 // one launcher for both kernels (epi 3, the RoPE step, is gemv's alone and launched where it is bound)
-void gemv_launch(bool skinny, int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale,
+void gemv_launch(int kern, int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale,
                  const void* b, void* y, int64_t ldy, int N, int K, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
                  const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
                  const uint8_t* bscale = nullptr) {
-    if (skinny)
+    if (kern == kWide) {
+        // the K-split rule's fp32 partial sums: a per-call buffer of the caching allocator (stream-ordered, so it is
+        // safe to release on return, and graph-safe: under capture it comes from the graph's pool)
+        const int64_t bytes = sa_launch::wide_workspace(bscale ? 2 : scale ? 1 : 0, M, N, K, epi, norm_w != nullptr);
+        at::Tensor ws;
+        if (bytes > 0) ws = at::empty({bytes}, at::TensorOptions().dtype(at::kByte).device(at::kCUDA));
+        sa_launch::wide(dtype, M, x, ldx, W, ldw, scale, b, y, ldy, N, K, cur_stream(), epi, res, ldr, norm_w, norm_add,
+                        norm_sum, eps, bscale, bytes > 0 ? (float*)ws.data_ptr() : nullptr);
+    } else if (kern == kSkinny)
         sa_launch::skinny(dtype, M, x, ldx, W, ldw, scale, b, y, ldy, N, K, cur_stream(), epi, res, ldr, norm_w, norm_add,
                           norm_sum, eps, bscale);
     else
@@ -508,11 +519,11 @@ void gemv_launch(bool skinny, int dtype, int M, const void* x, int64_t ldx, cons
 }
 
 at::Tensor gemv_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
-                     const c10::optional<at::Tensor>& bias, bool skinny = false) {
-    TORCH_CHECK(gemv_operands_ok(x, W, scale, skinny), name, ": unsupported operands ",
+                     const c10::optional<at::Tensor>& bias, int kern = kGemv) {
+    TORCH_CHECK(gemv_operands_ok(x, W, scale, kern), name, ": unsupported operands ",
                 is_w4(scale) ? "(x bf16 [M, K], codes uint8 [N, K / 2] in whole rows, scales uint8 [N, K / 32] contiguous, K % 32 == 0"
                 : scale ? "(x bf16 [M, K], Q e4m3fn [N, K], scale fp32 [N], K % 16 == 0, 16-byte aligned rows"
-                      : "(x [M, K], W [N, K], bf16/fp16, K % 8 == 0, aligned", skinny ? ", M <= 16)" : ", M <= 4)");
+                      : "(x [M, K], W [N, K], bf16/fp16, K % 8 == 0, aligned", kern == kWide ? ", M <= 64)" : kern == kSkinny ? ", M <= 16)" : ", M <= 4)");
     const at::DeviceGuard g(x.device());
     const int64_t M = x.size(0), N = W.size(0), K = x.size(1);
     const void* bp = nullptr;
@@ -523,20 +534,20 @@ at::Tensor gemv_impl(const char* name, const at::Tensor& x, const at::Tensor& W,
         bp = bc.data_ptr();
     }
     auto y = at::empty({M, N}, x.options());
-    gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), bp,
+    gemv_launch(kern, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), bp,
                 y.data_ptr(), N, (int)N, (int)K, 0, nullptr, 0, nullptr, nullptr, nullptr, 0.f, bscale_ptr(scale));
     return y;
 }
 // decode epilogues: y = rnd(x W^T) + res  (res [M, N]) ...
 at::Tensor gemv_residual_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
-                              const at::Tensor& res, bool skinny = false) {
-    TORCH_CHECK(gemv_operands_ok(x, W, scale, skinny), name, ": unsupported operands");
+                              const at::Tensor& res, int kern = kGemv) {
+    TORCH_CHECK(gemv_operands_ok(x, W, scale, kern), name, ": unsupported operands");
     const int64_t M = x.size(0), N = W.size(0), K = x.size(1);
     TORCH_CHECK(res.is_cuda() && res.dim() == 2 && res.size(0) == M && res.size(1) == N && res.stride(1) == 1 &&
                     res.scalar_type() == x.scalar_type(), name, ": res must be [M, N] of the input dtype");
     const at::DeviceGuard g(x.device());
     auto y = at::empty({M, N}, x.options());
-    gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
+    gemv_launch(kern, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
                 y.data_ptr(), N, (int)N, (int)K, 1, res.data_ptr(), res.stride(0), nullptr, nullptr, nullptr, 0.f,
                 bscale_ptr(scale));
     return y;
@@ -544,12 +555,12 @@ at::Tensor gemv_residual_impl(const char* name, const at::Tensor& x, const at::T
 // ... and SwiGLU over W = [gate; up] ([2F, K]): y[:, n] = silu(x W_gate^T)[n] * (x W_up^T)[n], rounded as gemv + swiglu
 // (FP8: scale [2F], the halves keep their own row scales)
 at::Tensor gemv_swiglu_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor* scale,
-                            bool skinny = false) {
-    TORCH_CHECK(gemv_operands_ok(x, W, scale, skinny) && W.size(0) % 2 == 0, name, ": unsupported operands");
+                            int kern = kGemv) {
+    TORCH_CHECK(gemv_operands_ok(x, W, scale, kern) && W.size(0) % 2 == 0, name, ": unsupported operands");
     const int64_t M = x.size(0), F = W.size(0) / 2, K = x.size(1);
     const at::DeviceGuard g(x.device());
     auto y = at::empty({M, F}, x.options());
-    gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
+    gemv_launch(kern, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
                 y.data_ptr(), F, (int)F, (int)K, 2, nullptr, 0, nullptr, nullptr, nullptr, 0.f, bscale_ptr(scale));
     return y;
 }
@@ -558,8 +569,8 @@ at::Tensor gemv_swiglu_impl(const char* name, const at::Tensor& x, const at::Ten
 // kernel when add is given
 std::vector<at::Tensor> gemv_norm_impl(const char* name, const at::Tensor& x, const c10::optional<at::Tensor>& add,
                                        const at::Tensor& gamma, double eps, const at::Tensor& W, const at::Tensor* scale,
-                                       int64_t epi, bool skinny = false) {
-    TORCH_CHECK(gemv_norm_operands_ok(x, W, scale, gamma, skinny) && (epi == 0 || (epi == 2 && W.size(0) % 2 == 0)), name,
+                                       int64_t epi, int kern = kGemv) {
+    TORCH_CHECK(gemv_norm_operands_ok(x, W, scale, gamma, kern) && (epi == 0 || (epi == 2 && W.size(0) % 2 == 0)), name,
                 ": unsupported operands");
     const int64_t M = x.size(0), K = x.size(1), N = epi == 2 ? W.size(0) / 2 : W.size(0);
     const at::DeviceGuard g(x.device());
@@ -573,7 +584,7 @@ std::vector<at::Tensor> gemv_norm_impl(const char* name, const at::Tensor& x, co
         ap = add->data_ptr();
     }
     auto y = at::empty({M, N}, x.options());
-    gemv_launch(skinny, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
+    gemv_launch(kern, dt(x), (int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(scale), nullptr,
                 y.data_ptr(), N, (int)N, (int)K, (int)epi, nullptr, 0, gamma.data_ptr(), ap, ap ? s.data_ptr() : nullptr,
                 (float)eps, bscale_ptr(scale));
     return {s, y};
@@ -619,46 +630,86 @@ std::vector<at::Tensor> gemv_w8_norm(const at::Tensor& x, c10::optional<at::Tens
 }
 
 // the same twelve entry points on the MFMA kernel, M <= 16 (skinny.hip)
-bool skinny_ok(const at::Tensor& x, const at::Tensor& W) { return gemv_operands_ok(x, W, nullptr, true); }
+bool skinny_ok(const at::Tensor& x, const at::Tensor& W) { return gemv_operands_ok(x, W, nullptr, kSkinny); }
 at::Tensor skinny(const at::Tensor& x, const at::Tensor& W, c10::optional<at::Tensor> bias) {
-    return gemv_impl("skinny", x, W, nullptr, bias, true);
+    return gemv_impl("skinny", x, W, nullptr, bias, kSkinny);
 }
 at::Tensor skinny_residual(const at::Tensor& x, const at::Tensor& W, const at::Tensor& res) {
-    return gemv_residual_impl("skinny_residual", x, W, nullptr, res, true);
+    return gemv_residual_impl("skinny_residual", x, W, nullptr, res, kSkinny);
 }
-at::Tensor skinny_swiglu(const at::Tensor& x, const at::Tensor& W) { return gemv_swiglu_impl("skinny_swiglu", x, W, nullptr, true); }
+at::Tensor skinny_swiglu(const at::Tensor& x, const at::Tensor& W) { return gemv_swiglu_impl("skinny_swiglu", x, W, nullptr, kSkinny); }
 bool skinny_norm_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor& gamma) {
-    return gemv_norm_operands_ok(x, W, nullptr, gamma, true);
+    return gemv_norm_operands_ok(x, W, nullptr, gamma, kSkinny);
 }
 std::vector<at::Tensor> skinny_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
                                     double eps, const at::Tensor& W, int64_t epi) {
-    return gemv_norm_impl("skinny_norm", x, add, gamma, eps, W, nullptr, epi, true);
+    return gemv_norm_impl("skinny_norm", x, add, gamma, eps, W, nullptr, epi, kSkinny);
 }
 bool skinny_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
-    return scale.dim() == 1 && gemv_operands_ok(x, Q, &scale, true);
+    return scale.dim() == 1 && gemv_operands_ok(x, Q, &scale, kSkinny);
 }
 at::Tensor skinny_w8(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, c10::optional<at::Tensor> bias) {
     TORCH_CHECK(scale.dim() == 1, "skinny_w8: scale must be one fp32 per row [N]");
-    return gemv_impl("skinny_w8", x, Q, &scale, bias, true);
+    return gemv_impl("skinny_w8", x, Q, &scale, bias, kSkinny);
 }
 at::Tensor skinny_w8_residual(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& res) {
     TORCH_CHECK(scale.dim() == 1, "skinny_w8_residual: scale must be one fp32 per row [N]");
-    return gemv_residual_impl("skinny_w8_residual", x, Q, &scale, res, true);
+    return gemv_residual_impl("skinny_w8_residual", x, Q, &scale, res, kSkinny);
 }
 at::Tensor skinny_w8_swiglu(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
     TORCH_CHECK(scale.dim() == 1, "skinny_w8_swiglu: scale must be one fp32 per row [N]");
-    return gemv_swiglu_impl("skinny_w8_swiglu", x, Q, &scale, true);
+    return gemv_swiglu_impl("skinny_w8_swiglu", x, Q, &scale, kSkinny);
 }
 bool skinny_w8_norm_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& gamma) {
-    return scale.dim() == 1 && gemv_norm_operands_ok(x, Q, &scale, gamma, true);
+    return scale.dim() == 1 && gemv_norm_operands_ok(x, Q, &scale, gamma, kSkinny);
 }
 std::vector<at::Tensor> skinny_w8_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
                                        double eps, const at::Tensor& Q, const at::Tensor& scale, int64_t epi) {
     TORCH_CHECK(scale.dim() == 1, "skinny_w8_norm: scale must be one fp32 per row [N]");
-    return gemv_norm_impl("skinny_w8_norm", x, add, gamma, eps, Q, &scale, epi, true);
+    return gemv_norm_impl("skinny_w8_norm", x, add, gamma, eps, Q, &scale, epi, kSkinny);
 }
 
-// MXFP4 weights on both kernels: (codes [N, K / 2], scales [N, K / 32]) in place of (Q, scale)
+// ... and on the LDS-shared-x MFMA kernel, M <= 64 (wide.hip): the same workers with kern = kWide
+bool wide_ok(const at::Tensor& x, const at::Tensor& W) { return gemv_operands_ok(x, W, nullptr, kWide); }
+at::Tensor wide(const at::Tensor& x, const at::Tensor& W, c10::optional<at::Tensor> bias) {
+    return gemv_impl("wide", x, W, nullptr, bias, kWide);
+}
+at::Tensor wide_residual(const at::Tensor& x, const at::Tensor& W, const at::Tensor& res) {
+    return gemv_residual_impl("wide_residual", x, W, nullptr, res, kWide);
+}
+at::Tensor wide_swiglu(const at::Tensor& x, const at::Tensor& W) { return gemv_swiglu_impl("wide_swiglu", x, W, nullptr, kWide); }
+bool wide_norm_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor& gamma) {
+    return gemv_norm_operands_ok(x, W, nullptr, gamma, kWide);
+}
+std::vector<at::Tensor> wide_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
+                                  double eps, const at::Tensor& W, int64_t epi) {
+    return gemv_norm_impl("wide_norm", x, add, gamma, eps, W, nullptr, epi, kWide);
+}
+bool wide_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    return scale.dim() == 1 && gemv_operands_ok(x, Q, &scale, kWide);
+}
+at::Tensor wide_w8(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, c10::optional<at::Tensor> bias) {
+    TORCH_CHECK(scale.dim() == 1, "wide_w8: scale must be one fp32 per row [N]");
+    return gemv_impl("wide_w8", x, Q, &scale, bias, kWide);
+}
+at::Tensor wide_w8_residual(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& res) {
+    TORCH_CHECK(scale.dim() == 1, "wide_w8_residual: scale must be one fp32 per row [N]");
+    return gemv_residual_impl("wide_w8_residual", x, Q, &scale, res, kWide);
+}
+at::Tensor wide_w8_swiglu(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    TORCH_CHECK(scale.dim() == 1, "wide_w8_swiglu: scale must be one fp32 per row [N]");
+    return gemv_swiglu_impl("wide_w8_swiglu", x, Q, &scale, kWide);
+}
+bool wide_w8_norm_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, const at::Tensor& gamma) {
+    return scale.dim() == 1 && gemv_norm_operands_ok(x, Q, &scale, gamma, kWide);
+}
+std::vector<at::Tensor> wide_w8_norm(const at::Tensor& x, c10::optional<at::Tensor> add, const at::Tensor& gamma,
+                                     double eps, const at::Tensor& Q, const at::Tensor& scale, int64_t epi) {
+    TORCH_CHECK(scale.dim() == 1, "wide_w8_norm: scale must be one fp32 per row [N]");
+    return gemv_norm_impl("wide_w8_norm", x, add, gamma, eps, Q, &scale, epi, kWide);
+}
+
+// MXFP4 weights on the three kernels: (codes [N, K / 2], scales [N, K / 32]) in place of (Q, scale)
 #define SA_W4_ENTRY(pre, sk)                                                                                           \
     bool pre##_w4_ok(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S) {                                  \
         return S.dim() == 2 && gemv_operands_ok(x, C, &S, sk);                                                         \
@@ -683,8 +734,9 @@ std::vector<at::Tensor> skinny_w8_norm(const at::Tensor& x, c10::optional<at::Te
         TORCH_CHECK(S.dim() == 2, #pre "_w4_norm: scales must be [N, K / 32]");                                        \
         return gemv_norm_impl(#pre "_w4_norm", x, add, gamma, eps, C, &S, epi, sk);                                    \
     }
-SA_W4_ENTRY(gemv, false)
-SA_W4_ENTRY(skinny, true)
+SA_W4_ENTRY(gemv, kGemv)
+SA_W4_ENTRY(skinny, kSkinny)
+SA_W4_ENTRY(wide, kWide)
 #undef SA_W4_ENTRY
 void gemv_w4_rule(int64_t rpw, int64_t ks) {
     TORCH_CHECK((rpw == 0 && ks == 0) || ((rpw == 1 || rpw == 2 || rpw == 4) && (ks == 1 || ks == 4)), "gemv_w4_rule");
@@ -1142,7 +1194,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("codes"), py::arg("scales"), py::arg("epi") = 0);
     SA_W4_DEF(gemv)
     SA_W4_DEF(skinny)
+    SA_W4_DEF(wide)
 #undef SA_W4_DEF
+    m.def("wide_ok", &wide_ok, "whether wide supports these operands");
+    m.def("wide", &wide, "y = x W^T (+ b) for at most 64 rows of x on the LDS-shared-x MFMA weight-streaming kernel (batched decode)",
+          py::arg("x"), py::arg("W"), py::arg("bias") = py::none());
+    m.def("wide_residual", &wide_residual, "y = x W^T + res for at most 64 rows (decode down / o-projection + residual)");
+    m.def("wide_swiglu", &wide_swiglu, "y = silu(x Wg^T) * (x Wu^T) for W = [Wg; Wu], at most 64 rows (decode)");
+    m.def("wide_norm_ok", &wide_norm_ok, "whether wide_norm supports these operands");
+    m.def("wide_norm", &wide_norm, "(s, wide(rms_norm(s), W)) with s = x (+ add); epi 0 plain, 2 SwiGLU (decode)",
+          py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("W"), py::arg("epi") = 0);
+    m.def("wide_w8_ok", &wide_w8_ok, "whether the FP8-weight wide kernel supports these operands");
+    m.def("wide_w8", &wide_w8, "y = x (scale * Q)^T (+ b) for at most 64 bf16 rows of x, Q e4m3fn codes, scale fp32 per row",
+          py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("bias") = py::none());
+    m.def("wide_w8_residual", &wide_w8_residual, "wide_w8 + res (decode down / o-projection + residual)");
+    m.def("wide_w8_swiglu", &wide_w8_swiglu, "silu(x Wg^T) * (x Wu^T) over FP8 [Wg; Wu] with per-row scales (decode)");
+    m.def("wide_w8_norm_ok", &wide_w8_norm_ok, "whether wide_w8_norm supports these operands");
+    m.def("wide_w8_norm", &wide_w8_norm, "(s, wide_w8(rms_norm(s), Q, scale)) with s = x (+ add); epi 0 plain, 2 SwiGLU",
+          py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("q"), py::arg("scale"), py::arg("epi") = 0);
     m.def("gemv_w4_rule", &gemv_w4_rule, "A/B switch of tools/gemv_bench.py: force the MXFP4 GEMV's (rows per wave, waves per row); (0, 0) restores its rules");
     m.def("skinny_ok", &skinny_ok, "whether skinny supports these operands");
     m.def("skinny", &skinny, "y = x W^T (+ b) for at most 16 rows of x on the MFMA weight-streaming kernel (batched decode)",

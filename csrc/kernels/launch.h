@@ -207,4 +207,14 @@ void skinny(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t
             void* y, int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
             const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
             const uint8_t* bscale = nullptr);
+// wide.hip: the same layer, arguments, formats and epilogues for M <= 64 rows: x goes through LDS once per workgroup
+// and every weight fragment feeds ceil(M / 16) MFMAs.  Row m of y is bitwise the same for every M and whatever the other
+// rows hold; rows >= M of x / norm_add / res are never read.  Where the launch rules split K across workgroups (small
+// N), ws must point at wide_workspace(fmt, ...) bytes of device memory, 16-byte aligned, owned by this call until it
+// has run (fmt 0 dense, 1 FP8, 2 MXFP4; 0 bytes: no workspace needed).
+int64_t wide_workspace(int fmt, int M, int N, int K, int epi, bool norm);
+void wide(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale, const void* b,
+          void* y, int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
+          const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
+          const uint8_t* bscale = nullptr, float* ws = nullptr);
 }  // namespace sa_launch

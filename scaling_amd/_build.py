@@ -97,6 +97,9 @@ def _check_kernel_stubs(so: Path) -> None:
 _NO_SLP = ["-fno-slp-vectorize"]
 _FILE_FLAGS: dict[str, list[str]] = {f: _NO_SLP for f in ("flash_fwd.hip", "flash_bwd.hip", "swiglu_rope.hip", "norm.hip",
                                                            "xent_embed_optim.hip", "elementwise.hip")}
+# wide.hip: no packed-fp32 instructions at all (the staging arithmetic of its NORM prologue is fp32 on whole fragments,
+# which the backend would otherwise pack)
+_FILE_FLAGS["wide.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def _env_file_flags() -> dict[str, list[str]]:

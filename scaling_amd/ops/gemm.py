@@ -16,7 +16,8 @@ the cached transpose and ``mm`` the input gradient ``dY W`` without it: at most 
 run the weight-streaming GEMV kernel (``csrc/kernels/gemv.hip``; its FP8 form for a weight that carries a valid
 FP8 copy, ``ops/quant.py``); inside ``skinny_gemm()`` (opt-in, batched decoding) ``SKINNY_MIN_ROWS`` to 16 rows run
 the MFMA weight-streaming kernel (``csrc/kernels/skinny.hip``: the same forms and weight formats, a time that does
-not grow with the row count, and row m of its result bitwise independent of the other rows); small products (<= ``SCALING_AMD_LT_SMALL_FLOP``
+not grow with the row count, and row m of its result bitwise independent of the other rows) and, with ``wide=True``,
+17 to 64 rows the wide MFMA kernel (``csrc/kernels/wide.hip``: x staged through LDS once per workgroup); small products (<= ``SCALING_AMD_LT_SMALL_FLOP``
 multiply-adds, 2^33 by default: none of the 7B step's) go through cached hipBLASLt plans (``csrc/blaslt.cpp``); the
 rest are plain library GEMMs (hipBLASLt through torch, TunableOp table ``scaling_amd/tuning/gemm_gfx950.csv``).  A hand-written NT GEMM with fused SwiGLU epilogues (rounds 3-5) stayed
 1-6 % behind hipBLASLt at every 7B shape and lost in the step even with its epilogues
@@ -67,25 +68,31 @@ SKINNY_MAX_ROWS = 16
 # the B = 2 step: 4.33 ms against the GEMV's 3.50, profiles/decode_skinny_ab_min2.jsonl); one and two rows stay on the GEMV
 SKINNY_MIN_ROWS = 3
 _skinny = False
+# the most rows of the LDS-shared-x MFMA kernel (csrc/kernels/wide.hip), taken inside skinny_gemm(wide=True) by the
+# row counts above SKINNY_MAX_ROWS
+WIDE_MAX_ROWS = 64
+_wide = False
 
 
 @contextlib.contextmanager
-def skinny_gemm(enabled: bool = True) -> Iterator[None]:
+def skinny_gemm(enabled: bool = True, wide: bool = False) -> Iterator[None]:
     """Inside, decode-sized linear layers of ``SKINNY_MIN_ROWS`` to ``SKINNY_MAX_ROWS`` rows run the MFMA kernel
-    (``ext().skinny*``) and ``decode_rows_limit()`` is 16.  Nestable; the previous state is restored on exit and on an
-    exception.  Outside nothing changes."""
-    global _skinny
-    prev = _skinny
-    _skinny = bool(enabled)
+    (``ext().skinny*``) and ``decode_rows_limit()`` is 16; with ``wide=True`` 17 to ``WIDE_MAX_ROWS`` rows also run the
+    wide MFMA kernel (``ext().wide*``) and the limit is 64.  Nestable; the previous state of both flags is restored on
+    exit and on an exception.  Outside nothing changes."""
+    global _skinny, _wide
+    prev = _skinny, _wide
+    _skinny, _wide = bool(enabled), bool(enabled) and bool(wide)
     try:
         yield
     finally:
-        _skinny = prev
+        _skinny, _wide = prev
 
 
 def decode_rows_limit() -> int:
-    """The most rows the fused decode paths (weight-streaming kernels + epilogues) take: 4, or 16 inside ``skinny_gemm()``."""
-    return SKINNY_MAX_ROWS if _skinny else GEMV_MAX_ROWS
+    """The most rows the fused decode paths (weight-streaming kernels + epilogues) take: 4, 16 inside ``skinny_gemm()``,
+    64 inside ``skinny_gemm(wide=True)``."""
+    return WIDE_MAX_ROWS if _wide else SKINNY_MAX_ROWS if _skinny else GEMV_MAX_ROWS
 
 
 def use_skinny(rows: int) -> bool:
@@ -93,10 +100,16 @@ def use_skinny(rows: int) -> bool:
     return _skinny and (rows >= SKINNY_MIN_ROWS or rows > GEMV_MAX_ROWS) and rows <= SKINNY_MAX_ROWS
 
 
+def use_wide(rows: int) -> bool:
+    """Whether ``rows`` decode rows run the wide MFMA kernel: 17..64 inside ``skinny_gemm(wide=True)``."""
+    return _wide and SKINNY_MAX_ROWS < rows <= WIDE_MAX_ROWS
+
+
 def decode_kernel(rows: int, suffix: str = "") -> Callable:
-    """``ext().gemv<suffix>`` or, where ``use_skinny(rows)``, ``ext().skinny<suffix>``: the two kernels bind the same
-    names with the same signatures (``_ok``, ``_residual``, ``_swiglu``, ``_norm``, ``_w8...``, ``_w4...``)."""
-    return getattr(ext(), ("skinny" if use_skinny(rows) else "gemv") + suffix)
+    """``ext().gemv<suffix>`` or, where ``use_skinny(rows)``, ``ext().skinny<suffix>`` or, where ``use_wide(rows)``,
+    ``ext().wide<suffix>``: the three kernels bind the same names with the same signatures (``_ok``, ``_residual``,
+    ``_swiglu``, ``_norm``, ``_w8...``, ``_w4...``)."""
+    return getattr(ext(), ("wide" if use_wide(rows) else "skinny" if use_skinny(rows) else "gemv") + suffix)
 # products of at most this many multiply-adds go through cached hipBLASLt plans (csrc/blaslt.cpp): torch's path
 # re-plans every call (~25-30 us of host time), which only a host-bound small model notices; 0 disables
 _LT_SMALL = int(os.environ.get("SCALING_AMD_LT_SMALL_FLOP", str(1 << 33)))
@@ -132,14 +145,15 @@ def mm_nt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
            wq: Optional[tuple[str, torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """``F.linear(x, w, b)``; decode-sized inputs (<= 4 rows) on the GEMV kernel, inside ``skinny_gemm()``
-    ``SKINNY_MIN_ROWS`` to 16 rows on the MFMA kernel under the same conditions.
+    ``SKINNY_MIN_ROWS`` to 16 rows on the MFMA kernel and inside ``skinny_gemm(wide=True)`` 17 to 64 rows on the wide
+    MFMA kernel, under the same conditions.
 
     The GEMV kernel is a raw op without autograd, so it only serves calls that build no graph (grad mode off, or
     no operand requiring grad); a tiny training micro-batch through a tied head keeps ``F.linear``'s backward.
 
     A weight quantised by ``ops.quant`` (``wq``: its valid copy with the suffix of the bindings that take it,
     ``("_w8", q, scale)`` or ``("_w4", codes, scales)``, looked up on ``w`` when not given) streams the copy through
-    that format's kernels (``csrc/kernels/gemv.hip``, ``skinny.hip``) on that
+    that format's kernels (``csrc/kernels/gemv.hip``, ``skinny.hip``, ``wide.hip``) on that
     same branch; ``w`` holds the dequantised values, so every other branch computes the same function."""
     K = x.shape[-1]
     rows = x.numel() // K if K else 0

@@ -22,6 +22,13 @@ not pick the same algorithm, so graph tokens could differ from eager tokens.
 row count and whose rows do not depend on each other, and the graph limit becomes 16 rows.  Above 16 rows the eager
 loop runs the library path as without the flag.
 
+``wide_batch=True`` (opt-in, implies the skinny path for 3..16 rows) runs every step inside
+``ops.gemm.skinny_gemm(wide=True)``: 17 to ``ops.gemm.WIDE_MAX_ROWS`` (64) rows take the wide MFMA kernels
+(``csrc/kernels/wide.hip``: x staged through LDS once per workgroup, every weight fragment feeding up to four MFMAs; the
+same forms, quantised copies and fused epilogues, rows bitwise independent of each other) and the graph limit becomes
+64 rows.  A request's tokens may differ between a B <= 16 and a B > 16 run: different kernels with different summation
+orders serve them (as already between the GEMV and the skinny kernel).
+
 Sampling: the first token of all rows is ONE ``sample_fn`` call on the stacked ``[B, 1, V]`` prefill logits (step 0,
 rows 0..B-1) and every later step is one call on the step's ``[B, 1, V]`` logits.  ``sample.Sampler`` hashes
 ``(seed, step, row)``, and the row index is part of the draw: a sampled batch does NOT repeat the text each prompt
@@ -57,7 +64,7 @@ class BatchDecoder:
     ``kv_cache="fp8_e4m3"`` (opt-in): the batched cache holds e4m3 codes with one power-of-two scale per cached row
     (``BatchStaticKVCacheFP8``: the prefilled rows are quantised here, every step appends quantised rows and the
     flash-decoding kernel reads the codes).  It touches attention only, so it composes with FP8 weights and
-    ``skinny_gemm``.
+    ``skinny_gemm`` and ``wide_batch`` (the module docstring: 17..64 rows on the wide MFMA kernels).
 
     ``page_size`` (opt-in, a multiple of 32): the cache is a ``PagedKVCache`` (``PagedKVCacheFP8``) of ``num_pages``
     pages (default: the parking pages plus ``ceil(capacity / page_size)`` pages per row) instead of one slab per row.
@@ -68,9 +75,10 @@ class BatchDecoder:
     def __init__(self, module: Any, prompt_lengths: Sequence[int], max_tokens: int, first_tokens: torch.Tensor,
                  sample_fn: Callable[[torch.Tensor], torch.Tensor], prefill_logits: torch.Tensor,
                  skinny_gemm: bool = False, kv_cache: Optional[str] = None, page_size: Optional[int] = None,
-                 num_pages: Optional[int] = None) -> None:
+                 num_pages: Optional[int] = None, wide_batch: bool = False) -> None:
         self.module = module
-        self.skinny_gemm = bool(skinny_gemm)
+        self.wide_batch = bool(wide_batch)
+        self.skinny_gemm = bool(skinny_gemm) or self.wide_batch
         self.kv_cache = check_kv_cache_scheme(kv_cache, "BatchDecoder")
         dev = first_tokens.device
         B = len(prompt_lengths)
@@ -138,7 +146,7 @@ class BatchDecoder:
     def _step(self) -> None:
         """One decode step, device ops only: feed ``tok`` at ``pos``, sample into ``tok``, record, advance."""
         B = self.batch_size
-        with gemm_ops.skinny_gemm(self.skinny_gemm):
+        with gemm_ops.skinny_gemm(self.skinny_gemm, wide=self.wide_batch):
             out = self.module.forward(self.batch)
         act = out.activations
         nxt = self.sample_fn(act).reshape(B, 1)
@@ -234,7 +242,8 @@ class ContinuousBatchDecoder:
     (``captures`` counts them).
 
     The step is ``BatchDecoder``'s: up to 4 rows on the GEMV kernels, 3..16 rows on the skinny MFMA kernels with
-    ``skinny_gemm=True``; under the graph ``max_batch`` is limited to 4, or 16 with ``skinny_gemm``.  ``kv_cache`` is
+    ``skinny_gemm=True``, 17..64 rows on the wide MFMA kernels with ``wide_batch=True`` (which implies ``skinny_gemm``);
+    under the graph ``max_batch`` is limited to 4, 16 with ``skinny_gemm`` or 64 with ``wide_batch``.  ``kv_cache`` is
     None or ``"fp8_e4m3"``.
 
     ``max_pages`` pages of ``page_size`` tokens bound one request (prompt + ``max_tokens``); ``num_pages`` sizes the pool
@@ -249,20 +258,23 @@ class ContinuousBatchDecoder:
     def __init__(self, module: Any, max_batch: int, page_size: int = 64, max_pages: int = 1,
                  num_pages: Optional[int] = None, sample_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
                  skinny_gemm: bool = False, kv_cache: Optional[str] = None, use_cuda_graph: bool = False,
-                 record_steps: int = 8) -> None:
+                 record_steps: int = 8, wide_batch: bool = False) -> None:
         from .sample import sample_argmax
 
         self.module = module
-        self.skinny_gemm = bool(skinny_gemm)
+        self.wide_batch = bool(wide_batch)
+        self.skinny_gemm = bool(skinny_gemm) or self.wide_batch
         self.kv_cache = check_kv_cache_scheme(kv_cache, "ContinuousBatchDecoder")
         page = check_page_size(page_size, "ContinuousBatchDecoder")
         B = int(max_batch)
         if B < 1 or max_pages < 1 or record_steps < 1:
             raise ValueError("ContinuousBatchDecoder: max_batch, max_pages and record_steps must be at least 1")
-        limit = gemm_ops.SKINNY_MAX_ROWS if skinny_gemm else gemm_ops.GEMV_MAX_ROWS
+        limit = (gemm_ops.WIDE_MAX_ROWS if wide_batch else gemm_ops.SKINNY_MAX_ROWS if skinny_gemm
+                 else gemm_ops.GEMV_MAX_ROWS)
         if use_cuda_graph and B > limit:
             raise ValueError(
-                f"ContinuousBatchDecoder: use_cuda_graph{' with skinny_gemm' if skinny_gemm else ''} supports at most "
+                f"ContinuousBatchDecoder: use_cuda_graph"
+                f"{' with wide_batch' if wide_batch else ' with skinny_gemm' if skinny_gemm else ''} supports at most "
                 f"{limit} rows, got {B}: above that the linear layers run library GEMMs, whose algorithm choice under "
                 "graph capture need not be the eager one; run without use_cuda_graph")
         self.attns = [m for m in module.modules() if isinstance(m, ParallelSelfAttention)]
@@ -297,7 +309,7 @@ class ContinuousBatchDecoder:
         self.record_steps = int(record_steps)
         self._slot = torch.zeros(1, dtype=torch.long, device=dev)
         # one parked step sizes the recording ring (vocabulary, logits dtype) and warms the lazy module state
-        with torch.no_grad(), gemm_ops.skinny_gemm(self.skinny_gemm):
+        with torch.no_grad(), gemm_ops.skinny_gemm(self.skinny_gemm, wide=self.wide_batch):
             act = self.module.forward(self.batch).activations
         self.rec_tokens = torch.zeros(self.record_steps, B, dtype=torch.long, device=dev)
         self.rec_logits = torch.zeros(self.record_steps, B, act.shape[-1], dtype=act.dtype, device=dev)
@@ -313,7 +325,7 @@ class ContinuousBatchDecoder:
         """One decode step of all rows, device ops only: feed ``tok`` at ``pos``, sample into ``tok``, record into the
         ring slot, advance the live rows."""
         B = self.batch_size
-        with gemm_ops.skinny_gemm(self.skinny_gemm):
+        with gemm_ops.skinny_gemm(self.skinny_gemm, wide=self.wide_batch):
             out = self.module.forward(self.batch)
         act = out.activations
         nxt = self.sample_fn(act).reshape(B, 1)

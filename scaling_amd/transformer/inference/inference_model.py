@@ -258,13 +258,14 @@ class TransformerInferenceModule(InferenceModule):
     def batch_decoder(self, max_tokens: int, input_tokens: Sequence[Sequence[int]],
                       sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                       skinny_gemm: bool = False, kv_cache: Optional[str] = None, page_size: Optional[int] = None,
-                      num_pages: Optional[int] = None) -> Any:
+                      num_pages: Optional[int] = None, wide_batch: bool = False) -> Any:
         """Prefills the prompts one at a time (prompt b under ``cache_index`` b), draws every row's first token with
         ONE ``sample_fn`` call on the stacked prefill logits and returns the ``batch_decode.BatchDecoder`` that decodes
         them together (not yet captured: call ``capture()`` for graph replay).  ``skinny_gemm``: its steps run inside
         ``ops.gemm.skinny_gemm()`` (the MFMA weight-streaming kernels for up to 16 rows, see ``generate_batch``).
         ``kv_cache``: None (bf16) or ``"fp8_e4m3"`` (see ``generate_batch``).  ``page_size``: the same static batch over
-        the paged KV cache (``num_pages`` pages; see ``generate_batch``)."""
+        the paged KV cache (``num_pages`` pages; see ``generate_batch``).  ``wide_batch``: the steps run inside
+        ``ops.gemm.skinny_gemm(wide=True)`` (the wide MFMA kernels for 17..64 rows, see ``generate_batch``)."""
         from ...core.nn.attention.attention import ParallelSelfAttention, check_kv_cache_scheme, check_page_size
         from .batch_decode import BatchDecoder
 
@@ -294,14 +295,16 @@ class TransformerInferenceModule(InferenceModule):
         prefill = torch.stack(last)  # [B, 1, V]
         first = sample_fn(prefill)
         return BatchDecoder(self, [len(p) for p in input_tokens], max_tokens, first, sample_fn, prefill,
-                            skinny_gemm=skinny_gemm, kv_cache=kv_cache, page_size=page_size, num_pages=num_pages)
+                            skinny_gemm=skinny_gemm, kv_cache=kv_cache, page_size=page_size, num_pages=num_pages,
+                            wide_batch=wide_batch)
 
     def generate_batch(self, max_tokens: int, input_texts: Optional[Sequence[str]] = None,
                        input_tokens: Optional[Sequence[Sequence[int]]] = None,
                        sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                        stop_tokens: Optional[Sequence[int]] = None,
                        use_cuda_graph: bool = False, skinny_gemm: bool = False,
-                       kv_cache: Optional[str] = None, page_size: Optional[int] = None) -> list[CompletionOutput]:
+                       kv_cache: Optional[str] = None, page_size: Optional[int] = None,
+                       wide_batch: bool = False) -> list[CompletionOutput]:
         """Completions for B prompts of any lengths, decoded together: one pass over the weights per step serves all
         B rows (``batch_decode.BatchDecoder``).  One device, always with the KV cache (flash attention kernel); the
         prompts are prefilled one at a time.  Stop tokens act per row: every row keeps stepping until all rows have
@@ -322,6 +325,15 @@ class TransformerInferenceModule(InferenceModule):
         16 prompts.  Every row of those kernels is bitwise independent of the other rows.  The flag is inert off the
         GPU, and above 16 rows the eager loop runs the library path as without it.
 
+        ``wide_batch`` (opt-in; implies ``skinny_gemm`` for 3..16 rows) decodes ``17 <= B <= ops.gemm.WIDE_MAX_ROWS``
+        (64) rows on the wide MFMA weight-streaming kernels (``csrc/kernels/wide.hip``;
+        ``ops.gemm.skinny_gemm(wide=True)``): x is staged through LDS once per workgroup and every weight fragment --
+        a decoded FP8 / MXFP4 piece included -- feeds up to four MFMAs.  Eager and graph alike, the same conditions,
+        quantised copies and fused epilogues; ``use_cuda_graph`` then takes up to 64 prompts and raises ``ValueError``
+        above that before any prefill.  Rows stay bitwise independent of each other, but a prompt's tokens may differ
+        between a B <= 16 and a B > 16 run: different kernels with different summation orders serve them (as already
+        between the GEMV and the skinny kernel).  It composes with ``quantize_weights``, ``kv_cache`` and ``page_size``.
+
         ``kv_cache="fp8_e4m3"`` (opt-in; default None, the bf16 cache): the decode steps keep K/V as OCP e4m3 codes with
         one fp32 power-of-two scale per cached row (one token of one kv head) -- ``hd + 4`` bytes instead of ``2 hd``
         -- written by the quantising RoPE + append kernel and read by the flash-decoding kernel
@@ -335,7 +347,7 @@ class TransformerInferenceModule(InferenceModule):
         lookup per 32-key tile; tokens and logits are the slab path's when ``longest prompt + max_tokens`` is a whole
         number of pages (the split plans then coincide).  ``generate_continuous`` refills finished rows on top of it."""
         from ...core.nn.attention.attention import check_kv_cache_scheme
-        from ...ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS
+        from ...ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS, WIDE_MAX_ROWS
 
         check_kv_cache_scheme(kv_cache, "generate_batch")
 
@@ -345,7 +357,13 @@ class TransformerInferenceModule(InferenceModule):
             assert self.tokenizer is not None
             input_tokens = [self.tokenizer.encode(t) for t in input_texts]
         assert input_tokens is not None
-        if use_cuda_graph and skinny_gemm and len(input_tokens) > SKINNY_MAX_ROWS:
+        if use_cuda_graph and wide_batch and len(input_tokens) > WIDE_MAX_ROWS:
+            raise ValueError(
+                f"generate_batch: use_cuda_graph with wide_batch supports at most {WIDE_MAX_ROWS} prompts, got "
+                f"{len(input_tokens)}: above that the linear layers run library GEMMs, whose algorithm choice under "
+                "graph capture need not be the eager one; run without use_cuda_graph")
+        skinny_gemm = skinny_gemm or wide_batch
+        if use_cuda_graph and not wide_batch and skinny_gemm and len(input_tokens) > SKINNY_MAX_ROWS:
             raise ValueError(
                 f"generate_batch: use_cuda_graph with skinny_gemm supports at most {SKINNY_MAX_ROWS} prompts, got "
                 f"{len(input_tokens)}: above that the linear layers run library GEMMs, whose algorithm choice under "
@@ -360,7 +378,7 @@ class TransformerInferenceModule(InferenceModule):
             assert self.tokenizer is not None, "If no tokenizer is provided, a stop token needs to be set manually"
             stop_tokens = [self.tokenizer.eos_token_id]
         dec = self.batch_decoder(max_tokens, input_tokens, sample_fn, skinny_gemm=skinny_gemm, kv_cache=kv_cache,
-                                 page_size=page_size)
+                                 page_size=page_size, wide_batch=wide_batch)
         if use_cuda_graph:
             dec.capture()
         outs = []
@@ -373,7 +391,7 @@ class TransformerInferenceModule(InferenceModule):
                            num_pages: Optional[int] = None,
                            sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                            use_cuda_graph: bool = False, skinny_gemm: bool = False,
-                           kv_cache: Optional[str] = None, record_steps: int = 8) -> Any:
+                           kv_cache: Optional[str] = None, record_steps: int = 8, wide_batch: bool = False) -> Any:
         """The ``batch_decode.ContinuousBatchDecoder`` of this model for a serving loop (``admit`` / ``step`` /
         ``release``, or ``serve``): ``max_batch`` rows over a paged KV cache whose requests take at most ``max_pages``
         pages of ``page_size`` tokens; captured once when ``use_cuda_graph``.  See ``generate_continuous``."""
@@ -383,14 +401,15 @@ class TransformerInferenceModule(InferenceModule):
             raise RuntimeError("generate_continuous: the model must sit on one device")
         return ContinuousBatchDecoder(self, max_batch, page_size=page_size, max_pages=max_pages, num_pages=num_pages,
                                       sample_fn=sample_fn, skinny_gemm=skinny_gemm, kv_cache=kv_cache,
-                                      use_cuda_graph=use_cuda_graph, record_steps=record_steps)
+                                      use_cuda_graph=use_cuda_graph, record_steps=record_steps, wide_batch=wide_batch)
 
     def generate_continuous(self, max_tokens: Any, input_texts: Optional[Sequence[str]] = None,
                             input_tokens: Optional[Sequence[Sequence[int]]] = None, max_batch: int = 4,
                             page_size: int = 64, num_pages: Optional[int] = None,
                             sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                             stop_tokens: Optional[Sequence[int]] = None, use_cuda_graph: bool = False,
-                            skinny_gemm: bool = False, kv_cache: Optional[str] = None) -> list[CompletionOutput]:
+                            skinny_gemm: bool = False, kv_cache: Optional[str] = None,
+                            wide_batch: bool = False) -> list[CompletionOutput]:
         """Completions for N requests (N may exceed ``max_batch``) by continuous batching over a paged KV cache:
         ``max_batch`` rows share every decode step, and a row whose request reaches a stop token or its own
         ``max_tokens`` (an int, or one int per request) is refilled with the next request while the others go on
@@ -400,8 +419,8 @@ class TransformerInferenceModule(InferenceModule):
         owns ``ceil(length / page_size)`` of them.  ``num_pages=None`` sizes the pool for ``max_batch`` sequences of the
         longest request (prompt + ``max_tokens``), plus one parking page per row.  A smaller pool raises
         ``RuntimeError`` when it runs out (there is no preemption).  ``use_cuda_graph`` captures the step once for the
-        whole stream and has ``generate_batch``'s limits on ``max_batch`` (4, or 16 with ``skinny_gemm``); ``kv_cache``
-        as in ``generate_batch``.  Greedy completions equal ``generate``'s per prompt up to the rounding of the batched
+        whole stream and has ``generate_batch``'s limits on ``max_batch`` (4, 16 with ``skinny_gemm``, 64 with
+        ``wide_batch``); ``kv_cache`` as in ``generate_batch``.  Greedy completions equal ``generate``'s per prompt up to the rounding of the batched
         kernels; with a seeded ``Sampler`` a draw depends on the row and the step a request happens to occupy."""
         if (input_texts is None) == (input_tokens is None):
             raise ValueError("generate_continuous: give either input_texts or input_tokens")
@@ -425,7 +444,7 @@ class TransformerInferenceModule(InferenceModule):
         longest = max(len(p) + m for p, m in zip(input_tokens, limits))
         dec = self.continuous_decoder(max_batch, page_size=page_size, max_pages=-(-longest // page_size),
                                       num_pages=num_pages, sample_fn=sample_fn, use_cuda_graph=use_cuda_graph,
-                                      skinny_gemm=skinny_gemm, kv_cache=kv_cache)
+                                      skinny_gemm=skinny_gemm, kv_cache=kv_cache, wide_batch=wide_batch)
         outs = []
         for tokens, logits in dec.serve(list(zip(input_tokens, limits)), stop_tokens):
             text = self.tokenizer.decode(tokens) if self.tokenizer is not None else None

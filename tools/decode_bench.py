@@ -1,13 +1,15 @@
 """Batch-1 decode latency on one GPU: eager cached generation vs HIP-graph-captured decoding, greedy or sampled.
 
     python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64] [--sampler T,K,P | torch:T,K,P]
-                                 [--weights fp8_e4m3 | mxfp4 | bf16,fp8_e4m3,mxfp4 [--lm-head]] [--batch B [--skinny]]
+                                 [--weights fp8_e4m3 | mxfp4 | bf16,fp8_e4m3,mxfp4 [--lm-head]] [--batch B [--skinny | --wide]]
                                  [--kv-cache bf16,fp8_e4m3 [--rounds N]] [--paged 0,64] [--continuous N]
 
 ``--batch B`` times batched generation instead (``generate_batch`` / ``BatchDecoder``): B random prompts of lengths
 ``prompt, prompt - 7, prompt - 14, ...`` decoded together; ms per step, tokens/s summed over the rows, and (B <= 4:
 the graph limit) the captured loop and ``graph_tokens_equal_eager``.  ``--skinny`` passes ``skinny_gemm=True`` to
-``batch_decoder``: the MFMA weight-streaming kernels (``csrc/kernels/skinny.hip``) and a graph limit of 16 rows.
+``batch_decoder``: the MFMA weight-streaming kernels (``csrc/kernels/skinny.hip``) and a graph limit of 16 rows;
+``--wide`` passes ``wide_batch=True`` (implies ``--skinny``): the wide MFMA kernels (``csrc/kernels/wide.hip``) for 17..64
+rows and a graph limit of 64.
 
 ``--weights fp8_e4m3`` decodes the model after ``quantize_weights()`` (FP8 weight-only decoding; ``--lm-head`` includes
 the LM head); ``weights_gib`` and ``graph_gb_per_s`` then count what one decode step streams (the FP8 copies in place of
@@ -68,6 +70,7 @@ def main() -> None:
     p.add_argument("--rounds", type=int, default=1, help="with --batch: repeat the --kv-cache list this many times")
     p.add_argument("--paged", default="0", help="with --batch: page size of the paged KV cache (0: slabs), or a comma list "
                    "measured alternately")
+    p.add_argument("--wide", action="store_true", help="with --batch: wide_batch=True (wide MFMA kernels, graph up to B = 64)")
     p.add_argument("--continuous", type=int, default=0, help="with --batch B --skinny: serve N requests by continuous "
                    "batching and by static groups of B")
     p.add_argument("--spread", default="32,256", help="with --continuous: range of the requests' max_tokens")
@@ -202,7 +205,7 @@ def continuous_bench(m, a, arch, sample_fn, timed, kv=None) -> None:
     nkv = arch.attention_num_kv_heads or arch.num_attention_heads
     hd = arch.hidden_size // arch.num_attention_heads
     per_token = arch.num_layers * 2 * nkv * (2 * hd if kv is None else hd + 4)
-    kw = dict(skinny_gemm=a.skinny, kv_cache=kv)
+    kw = dict(skinny_gemm=a.skinny, kv_cache=kv, wide_batch=a.wide)
     graph = next(m.parameters()).is_cuda
     longest = max(len(p) + mt for p, mt in reqs)
     m.generate_continuous(4, input_tokens=[p for p, _ in reqs[:B]], max_batch=B, page_size=page, stop_tokens=[],
@@ -225,7 +228,7 @@ def continuous_bench(m, a, arch, sample_fn, timed, kv=None) -> None:
     print(json.dumps({
         "metric": "continuous vs static batching, generated tokens/s", "requests": N, "rows": B, "model": a.model,
         "layers": arch.num_layers, "prompt": a.prompt, "max_tokens_range": [lo, hi], "tokens": total, "page": page,
-        "kv_cache": kv or "bf16", "skinny_gemm": a.skinny,
+        "kv_cache": kv or "bf16", "skinny_gemm": a.skinny, "wide_batch": a.wide,
         "continuous_s": round(tcont, 3), "continuous_tokens_per_s": round(total / tcont, 1), "continuous_steps": dec.steps_run,
         "static_s": round(tstat, 3), "static_tokens_per_s": round(total / tstat, 1), "static_steps": steps_static,
         "speedup": round(tstat / tcont, 2),
@@ -238,7 +241,7 @@ def continuous_bench(m, a, arch, sample_fn, timed, kv=None) -> None:
 def batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv=None, page=None) -> None:
     """``--batch B``: per-step time of the batched decode loop (prefills and capture excluded); ``kv``: the KV cache
     scheme (None: bf16); ``page``: the paged cache's page size (None: slabs)."""
-    from scaling_amd.ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS
+    from scaling_amd.ops.gemm import GEMV_MAX_ROWS, SKINNY_MAX_ROWS, WIDE_MAX_ROWS
 
     B, steps = a.batch, a.tokens
     if not hasattr(a, "prompts"):  # drawn once from the global stream (as ever): every setting and round decodes them
@@ -248,20 +251,20 @@ def batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv=None, page=Non
     hd = arch.hidden_size // arch.num_attention_heads
     kv_bytes = arch.num_layers * 2 * nkv * (2 * hd if kv is None else hd + 4)  # K and V, all layers, one token
     m.generate_batch(4, input_tokens=prompts, stop_tokens=[], sample_fn=sample_fn, skinny_gemm=a.skinny, kv_cache=kv,
-                     page_size=page)  # warm-up
-    dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv, page_size=page)
+                     page_size=page, wide_batch=a.wide)  # warm-up
+    dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv, page_size=page, wide_batch=a.wide)
     te, eager = timed(lambda: dec.run([], check_every=steps + 1))
     eager_ms = 1000.0 * te / steps
     weights = sum(p.numel() * p.element_size() for p in m.parameters())
     if quantised is not None:
         weights = weights - quantised["bf16_bytes"] + quantised["quantized_bytes"]
     res = {"metric": "batched decode ms/step", "batch": B, "sampler": mode, "model": a.model, "layers": arch.num_layers,
-           "prompt": a.prompt, "tokens": steps, "weights": a.weights, "skinny_gemm": a.skinny, "kv_cache": kv or "bf16",
+           "prompt": a.prompt, "tokens": steps, "weights": a.weights, "skinny_gemm": a.skinny, "wide_batch": a.wide, "kv_cache": kv or "bf16",
            "page_size": page or 0,
            "kv_bytes_per_token": kv_bytes, "eager_ms_per_step": round(eager_ms, 3),
            "eager_tokens_per_s": round(B * 1000.0 / eager_ms, 1), "weights_gib": round(weights / 2**30, 2)}
-    if B <= (SKINNY_MAX_ROWS if a.skinny else GEMV_MAX_ROWS):
-        dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv, page_size=page)
+    if B <= (WIDE_MAX_ROWS if a.wide else SKINNY_MAX_ROWS if a.skinny else GEMV_MAX_ROWS):
+        dec = m.batch_decoder(steps + 1, prompts, sample_fn, skinny_gemm=a.skinny, kv_cache=kv, page_size=page, wide_batch=a.wide)
         tc, _ = timed(dec.capture)
         tg, graph = timed(lambda: dec.run([], check_every=steps + 1))
         graph_ms = 1000.0 * tg / steps

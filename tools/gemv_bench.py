@@ -15,7 +15,11 @@ shapes in the forms the decode step runs them, each right beside its counterpart
 (the library GEMM alone, without the norm / SwiGLU / residual the fused forms include) at M = 8 and 16 -- bf16 and
 FP8 (``SKINNY_FORMATS=bf16`` for one of them; ``SKINNY_FORMATS=bf16,fp8,mxfp4`` adds the MXFP4 forms, ``SKINNY_ROWS``
 such as ``1,4,16`` picks the row counts), same process, same cold-cache protocol, ``PASSES`` (default 2) alternating
-passes."""
+passes.
+
+``WIDE=1``: the wide MFMA kernel (``csrc/kernels/wide.hip``) at M = 17, 32, 64 rows (``SKINNY_ROWS`` picks others) in
+the same forms, formats (``SKINNY_FORMATS``, default all three) and protocol, beside ``F.linear`` at the same M (what
+serves these rows without it) and the skinny kernel at 16 rows."""
 from __future__ import annotations
 
 import os
@@ -169,7 +173,7 @@ def main() -> None:
             print(f"{name:34s} {us:8.2f} us  {nb / us / 1e6 if nb else 0:6.2f} TB/s", flush=True)
 
 
-def skinny_main() -> None:
+def skinny_main(wide: bool = False) -> None:
     from scaling_amd.ops._ext import ext
 
     torch.manual_seed(0)
@@ -181,9 +185,9 @@ def skinny_main() -> None:
     # (name, weight shape, K, form); forms: n0 = norm + plain, n2 = add + norm + SwiGLU, res = + residual, plain
     layers = [("qkv norm", (3 * H, H), "n0"), ("o residual", (H, H), "res"), ("gate/up norm swiglu", (2 * F, H), "n2"),
               ("down residual", (H, F), "res"), ("head", (V, H), "plain")]
-    print(f"skinny vs gemv / F.linear, {'cold (weights cycled through > 1 GiB)' if cold else 'warm (one weight copy)'}",
+    print(f"{'wide vs F.linear / skinny at 16 rows' if wide else 'skinny vs gemv / F.linear'}, {'cold (weights cycled through > 1 GiB)' if cold else 'warm (one weight copy)'}",
           flush=True)
-    for fmt in os.environ.get("SKINNY_FORMATS", "bf16,fp8").split(","):
+    for fmt in os.environ.get("SKINNY_FORMATS", "bf16,fp8,mxfp4" if wide else "bf16,fp8").split(","):
         for name, shape, form in layers:
             ws = copies(shape, dev, dt, cold) if fmt == "bf16" else copies8(shape, dev, cold) if fmt == "fp8" else copies4(shape, dev, cold)
             w0 = ws[0]
@@ -191,12 +195,14 @@ def skinny_main() -> None:
             wl = copies(shape, dev, dt, cold) if fmt != "bf16" else ws  # F.linear streams bf16 either way
             N, K = shape
             for p in range(int(os.environ.get("PASSES", "2"))):
-                for M in (int(r) for r in os.environ.get("SKINNY_ROWS", "1,2,3,4,8,16").split(",")):
+                for M in (int(r) for r in os.environ.get("SKINNY_ROWS", "17,32,64" if wide else "1,2,3,4,8,16").split(",")):
                     x = torch.randn(M, K, device=dev, dtype=dt)
                     add = torch.randn(M, K, device=dev, dtype=dt)
                     res = torch.randn(M, N, device=dev, dtype=dt)
 
                     def call(kind, i, M=M, x=x, add=add, res=res):
+                        if kind == "skinny" and M > 16:  # (wide mode: the 16-row skinny call beside it)
+                            x, add, res = x[:16], add[:16], res[:16]
                         w = W(ws, i)
                         wa = w if isinstance(w, tuple) else (w,)
                         pre = kind + {"bf16": "", "fp8": "_w8", "mxfp4": "_w4"}[fmt]
@@ -208,7 +214,8 @@ def skinny_main() -> None:
                             return getattr(ext(), pre + "_residual")(x, *wa, res)
                         return getattr(ext(), pre)(x, *wa, None)
 
-                    row = [("skinny", timeit(lambda i: call("skinny", i)))]
+                    row = [("wide", timeit(lambda i: call("wide", i)))] if wide else []
+                    row.append(("skinny@16" if wide else "skinny", timeit(lambda i: call("skinny", i))))
                     if M <= 4:
                         row.append(("gemv", timeit(lambda i: call("gemv", i))))
                     else:
@@ -223,6 +230,8 @@ def skinny_main() -> None:
 if __name__ == "__main__":
     if os.environ.get("W4_RULES", "0") != "0":
         w4_rules_main()
+    elif os.environ.get("WIDE", "0") != "0":
+        skinny_main(wide=True)
     elif os.environ.get("SKINNY", "0") != "0":
         skinny_main()
     else:

@@ -4,7 +4,8 @@ inputs at the tests' shapes -- M = 1..4, one wave per row and four, full / tail-
 row-strided weight view and a row-strided x: run it under two builds (``SCALING_AMD_EXT_SO``) and diff the printed
 lines to check that a kernel change is bit-identical.  The same for the MFMA kernel's entry points
 (``csrc/kernels/skinny.hip``, ``skinny*`` / ``skinny_w8*``) at M = 1, 5, 16 and one shape per launch rule.
-The MXFP4 entry points (``gemv_w4*`` / ``skinny_w4*``) follow as lines tagged ``w4`` when the build has them, at the
+With ``WIDE=1`` the wide MFMA kernel's entry points (``csrc/kernels/wide.hip``, ``wide*``) follow at M = 1, 17, 64 and one
+shape per launch rule of its own.  The MXFP4 entry points (``gemv_w4*`` / ``skinny_w4*``) follow as lines tagged ``w4`` when the build has them, at the
 same shapes with K rounded up to a multiple of 32.
 
 usage: python tools/gemv_bits.py
@@ -104,27 +105,29 @@ def run(dt, fp8: bool, rope: bool, all_paths: bool) -> None:
                       f"err {int(err.item())}", flush=True)
 
 
-def run_skinny(dt, fp8: bool) -> None:
+def run_skinny(dt, fp8: bool, kern: str = "skinny") -> None:
     tag = "w8" if fp8 else {torch.bfloat16: "bf16", torch.float16: "fp16"}[dt]
-    fn = lambda name: getattr(ext(), name.replace("skinny", "skinny_w8", 1) if fp8 else name)  # noqa: E731
+    fn = lambda name: getattr(ext(), name.replace("skinny", kern + ("_w8" if fp8 else ""), 1))  # noqa: E731
     wargs = lambda w: quant.quantize_rows_fp8(w) if fp8 else (w,)  # noqa: E731
     # the tests' plain shapes, then one per launch rule: K split x 1 tile, K split x 2 tiles, no K split
-    for N, K in [(5, 16), (1003, 208), (64, 4112), (263, 528), (136, 528), (8200, 64), (32781, 64)]:
+    # (wide: K split, one chunk, two tiles per wave)
+    skinny_shapes = [(5, 16), (1003, 208), (64, 4112), (263, 528), (136, 528), (8200, 64), (32781, 64)]
+    for N, K in skinny_shapes if kern == "skinny" else [(136, 528), (77, 64), (32781, 288)]:
         wa, w2 = wargs(weight(N + K, N, K, dt)), wargs(weight(5 + N + K, 2 * N, K, dt))
         wv = (strided(wa[0], 64, 32),) + tuple(wa[1:])
         gam = (1 + 0.1 * randn(3 * K, K, dt=torch.float32)).to(dt)
-        for M in (1, 5, 16):
+        for M in (1, 5, 16) if kern == "skinny" else (1, 17, 64):
             x, add = randn(7 * N + K + M, M, K, dt=dt), randn(2 * (N + K) + M, M, K, dt=dt)
             b, res = randn(3 * N + 1, N, dt=dt), randn(4 * N + M, M, N, dt=dt)
             y = [fn("skinny")(xx, *ww, bb) for xx, ww, bb in ((x, wa, None), (x, wa, b), (x, wv, b), (strided(x, 24, 8), wa, b))]
-            print(f"{tag} skinny N={N} K={K} M={M}: y {digest(y[0])} bias {digest(y[1])} wview {digest(y[2])} "
+            print(f"{tag} {kern} N={N} K={K} M={M}: y {digest(y[0])} bias {digest(y[1])} wview {digest(y[2])} "
                   f"xview {digest(y[3])}", flush=True)
-            print(f"{tag} skinny_residual N={N} K={K} M={M}: y {digest(fn('skinny_residual')(x, *wa, res))}", flush=True)
-            print(f"{tag} skinny_swiglu F={N} K={K} M={M}: y {digest(fn('skinny_swiglu')(x, *w2))}", flush=True)
+            print(f"{tag} {kern}_residual N={N} K={K} M={M}: y {digest(fn('skinny_residual')(x, *wa, res))}", flush=True)
+            print(f"{tag} {kern}_swiglu F={N} K={K} M={M}: y {digest(fn('skinny_swiglu')(x, *w2))}", flush=True)
             for a in (None, add):
                 for epi, ww in ((0, wa), (2, w2)):
                     s, yn = fn("skinny_norm")(x, a, gam, 1e-5, *ww, epi)
-                    print(f"{tag} skinny_norm N={N} K={K} M={M} add={a is not None} epi={epi}: s {digest(s)} "
+                    print(f"{tag} {kern}_norm N={N} K={K} M={M} add={a is not None} epi={epi}: s {digest(s)} "
                           f"y {digest(yn)}", flush=True)
 
 
@@ -159,6 +162,9 @@ run(torch.bfloat16, fp8=True, rope=False, all_paths=True)
 run_skinny(torch.bfloat16, fp8=False)
 run_skinny(torch.float16, fp8=False)
 run_skinny(torch.bfloat16, fp8=True)
+if os.environ.get("WIDE", "0") != "0":
+    for dt, fp8 in ((torch.bfloat16, False), (torch.float16, False), (torch.bfloat16, True)):
+        run_skinny(dt, fp8, kern="wide")
 if hasattr(ext(), "gemv_w4"):
     run_w4()
 torch.cuda.synchronize()
