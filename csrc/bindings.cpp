@@ -913,6 +913,84 @@ std::vector<at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const a
     if (T > 0 && a.nseg > 0) sa_launch::fa_fwd(a, (int)D, (int)max_q, q.scalar_type() == at::kHalf, cur_stream());
     return {o, lse};
 }
+// chunk attention (flash_chunk.hip): query segments of any length over keys in a KV cache.  k_range int32 [nseg, 2] =
+// (first key row, key count) over a slab buffer, or (0, length) with block_table int32 [nseg, max_pages] + page_size
+// over a pool of pages; k_scale / v_scale: FP8 codes as in fa_fwd.  splits = 0: the plan; > 0 forces that many.
+std::vector<at::Tensor> fa_chunk(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& cu_q,
+                                 int64_t max_q, double scale, bool causal, int64_t window, int64_t local_heads,
+                                 int64_t max_k, const at::Tensor& k_range, const c10::optional<at::Tensor>& k_scale,
+                                 const c10::optional<at::Tensor>& v_scale, const c10::optional<at::Tensor>& block_table,
+                                 int64_t page_size, int64_t splits) {
+    const bool q8 = k_scale.has_value() || v_scale.has_value();
+    check_qkv(q, "q");
+    if (q8) {
+        TORCH_CHECK(k_scale.has_value() && v_scale.has_value(), "chunk_attn: k_scale and v_scale come together");
+        for (const at::Tensor* t : {&k, &v}) {
+            TORCH_CHECK(t->is_cuda() && t->dim() == 3 && t->stride(2) == 1, "chunk_attn: FP8 k / v must be [T, heads, D] with unit last stride");
+            TORCH_CHECK(fp8_codes(*t), "chunk_attn: with k_scale / v_scale, k and v must be uint8 or float8_e4m3fn codes");
+            TORCH_CHECK(t->stride(0) % 16 == 0 && t->stride(1) % 16 == 0 && (uintptr_t)t->data_ptr() % 16 == 0,
+                        "chunk_attn: FP8 k / v strides and addresses must be multiples of 16 bytes");
+        }
+        TORCH_CHECK(q.scalar_type() == at::kBFloat16, "chunk_attn: FP8 k / v need bfloat16 queries (an e4m3 code times its scale is exact in bfloat16, not in float16)");
+        for (const at::Tensor* s : {&*k_scale, &*v_scale})
+            TORCH_CHECK(s->is_cuda() && s->scalar_type() == at::kFloat && s->dim() == 2 && s->size(0) == k.size(1) &&
+                            s->size(1) == k.size(0) && s->stride(1) == 1 && s->stride(0) == k_scale->stride(0),
+                        "chunk_attn: k_scale / v_scale must be float32 GPU tensors [kv heads, key rows] with unit last stride");
+    } else {
+        check_qkv(k, "k"); check_qkv(v, "v");
+        TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type(), "chunk_attn: q/k/v dtypes differ");
+        for (const at::Tensor* t : {&k, &v}) TORCH_CHECK((uintptr_t)t->data_ptr() % 16 == 0, "chunk_attn: k / v addresses must be multiples of 16 bytes");
+    }
+    TORCH_CHECK((uintptr_t)q.data_ptr() % 16 == 0, "chunk_attn: q address must be a multiple of 16 bytes");
+    const int64_t D = q.size(2), T = q.size(0), H = q.size(1);
+    TORCH_CHECK(D == 32 || D == 64 || D == 128, "chunk_attn: head dim must be 32, 64 or 128");
+    TORCH_CHECK(k.size(2) == D && v.size(2) == D && k.size(1) == v.size(1) && k.size(1) > 0 && H % k.size(1) == 0 &&
+                v.size(0) == k.size(0), "chunk_attn: shapes");
+    TORCH_CHECK(cu_q.is_cuda() && cu_q.scalar_type() == at::kInt && cu_q.is_contiguous() && cu_q.numel() >= 1, "chunk_attn: cu_seqlens int32");
+    const int nseg = (int)cu_q.numel() - 1;
+    TORCH_CHECK(nseg <= 65535 && max_q >= 0 && splits >= 0 && k.size(0) < (int64_t)1 << 31, "chunk_attn: sizes");
+    TORCH_CHECK(k_range.is_cuda() && k_range.scalar_type() == at::kInt && k_range.is_contiguous() && k_range.dim() == 2 &&
+                k_range.size(0) == nseg && k_range.size(1) == 2, "chunk_attn: k_range must be a contiguous int32 GPU tensor [nseg, 2]");
+    const bool pg = block_table.has_value();
+    if (pg) {
+        TORCH_CHECK(page_size > 0 && page_size % 32 == 0, "chunk_attn: page_size must be a positive multiple of 32");
+        TORCH_CHECK(block_table->is_cuda() && block_table->scalar_type() == at::kInt && block_table->dim() == 2 &&
+                    block_table->size(0) == nseg && block_table->size(1) >= 1 && block_table->stride(1) == 1,
+                    "chunk_attn: block_table must be an int32 GPU tensor [nseg, max_pages] with unit last stride");
+        TORCH_CHECK(k.size(0) > 0 && k.size(0) % page_size == 0 && block_table->size(1) * page_size < (int64_t)1 << 31,
+                    "chunk_attn: with block_table, k / v must hold a whole number of pages (fewer than 2^31 rows)");
+    }
+    const at::DeviceGuard g(q.device());
+    auto o = at::empty({T, H, D}, q.options());
+    auto lse = at::empty({H, T}, q.options().dtype(at::kFloat));
+    if (T == 0 || nseg <= 0 || max_q == 0) return {o, lse};
+    DecArgs d{};
+    d.q = (const uint16_t*)q.data_ptr(); d.k = (const uint16_t*)k.data_ptr(); d.v = (const uint16_t*)v.data_ptr();
+    d.q_tok = q.stride(0); d.q_head = q.stride(1); d.k_tok = k.stride(0); d.k_head = k.stride(1);
+    d.v_tok = v.stride(0); d.v_head = v.stride(1);
+    d.cu_q = cu_q.data_ptr<int>(); d.cu_k = nullptr; d.k_range = k_range.data_ptr<int>(); d.k_rows = k.size(0);
+    if (q8) { d.k_scale = k_scale->data_ptr<float>(); d.v_scale = v_scale->data_ptr<float>(); d.s_head = k_scale->stride(0); }
+    d.nseg = nseg; d.Hq = (int)H; d.Hkv = (int)k.size(1); d.causal = causal ? 1 : 0; d.window = (int)window;
+    d.local_heads = local_heads < 0 ? (int)H : (int)local_heads;
+    d.scale_log2 = (float)(scale * 1.4426950408889634); d.Tq = T;
+    d.o = (uint16_t*)o.data_ptr(); d.o_tok = o.stride(0); d.o_head = o.stride(1); d.lse = lse.data_ptr<float>(); d.lse_stride = T;
+    if (pg) {
+        d.block_table = block_table->data_ptr<int>(); d.bt_stride = block_table->stride(0); d.page = (int)page_size;
+        d.num_pages = (int)(k.size(0) / page_size); d.max_pages = (int)block_table->size(1);
+    }
+    const int grp = d.Hq / d.Hkv;
+    const int64_t mk = max_k > 0 ? max_k : (pg ? block_table->size(1) * page_size : k.size(0));
+    sa_launch::fa_chunk_plan(max_q, mk, d.Hkv, grp, nseg, pg, (int)splits, d.split_keys, d.nsplit);
+    TORCH_CHECK((int64_t)d.Hkv * d.nsplit < (int64_t)1 << 31 && (max_q * grp + 127) / 128 <= 65535, "chunk_attn: grid too large");
+    at::Tensor part_o, part_ml;
+    if (d.nsplit > 1) {
+        part_o = at::empty({(int64_t)d.nsplit, T, H, D}, q.options().dtype(at::kFloat));
+        part_ml = at::empty({(int64_t)d.nsplit, T, H, 2}, q.options().dtype(at::kFloat));
+        d.part_o = part_o.data_ptr<float>(); d.part_ml = part_ml.data_ptr<float>();
+    }
+    sa_launch::fa_chunk(d, (int)D, q.scalar_type() == at::kHalf, (int)max_q, cur_stream());
+    return {o, lse};
+}
 std::vector<at::Tensor> fa_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                const at::Tensor& o, const at::Tensor& lse, const at::Tensor& cu_q, const at::Tensor& cu_k,
                                int64_t max_q, int64_t max_k, double scale, bool causal, int64_t window,
@@ -1263,5 +1341,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("src"), py::arg("scratch"), py::arg("bytes"), py::arg("us"), py::arg("nwg") = 16);
     m.def("dropout_add", &dropout_add, "residual + dropout(x) with a hashed keep mask", py::arg("x"), py::arg("res"), py::arg("p"), py::arg("seed"));
     m.def("fa_fwd", &fa_fwd, "flash attention forward (bf16/fp16, optional attention dropout)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("max_k") = -1, py::arg("k_range") = py::none(), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("page_size") = 0);
+    m.def("fa_chunk", &fa_chunk, "chunk attention over a KV cache (slab ranges or pages; bf16/fp16/FP8 keys), forward only", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("local_heads"), py::arg("max_k"), py::arg("k_range"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("page_size") = 0, py::arg("splits") = 0);
     m.def("fa_bwd", &fa_bwd, "flash attention backward (optional strided dq/dk/dv outputs)", py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("max_k"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(), py::arg("dv_out") = py::none(), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("rope_cos") = py::none(), py::arg("rope_sin") = py::none(), py::arg("rope_pos") = py::none(), py::arg("rope_dim") = 0, py::arg("rope_seq") = 1, py::arg("rope_interleaved") = false);
 }

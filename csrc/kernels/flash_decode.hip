@@ -392,6 +392,19 @@ void fa_decode_plan(int64_t max_k, int Hkv, int nseg, int& split_keys, int& nspl
     split_keys = (int)(per * 32);
     nsplit = (int)std::max<int64_t>(1, (max_k + split_keys - 1) / split_keys);
 }
+// the combine pass alone, for other kernels that write partials in this layout (flash_chunk.hip)
+void fa_decode_combine(const DecArgs& a, int D, bool f16, hipStream_t st) {
+    const dim3 grid((unsigned)a.Tq, a.Hq);
+    if (f16) {
+        if (D == 128) hipLaunchKernelGGL((fa_decode_combine_kernel<128, true>), grid, dim3(128), 0, st, a);
+        else if (D == 64) hipLaunchKernelGGL((fa_decode_combine_kernel<64, true>), grid, dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((fa_decode_combine_kernel<32, true>), grid, dim3(32), 0, st, a);
+    } else {
+        if (D == 128) hipLaunchKernelGGL((fa_decode_combine_kernel<128, false>), grid, dim3(128), 0, st, a);
+        else if (D == 64) hipLaunchKernelGGL((fa_decode_combine_kernel<64, false>), grid, dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((fa_decode_combine_kernel<32, false>), grid, dim3(32), 0, st, a);
+    }
+}
 void fa_decode(const DecArgs& a, int D, bool f16, hipStream_t st) {
     const int nseg = a.nseg;
     if (f16) {

@@ -119,6 +119,14 @@ struct DecArgs {
 namespace sa_launch {
 void fa_decode_plan(int64_t max_k, int Hkv, int nseg, int& split_keys, int& nsplit);
 void fa_decode(const DecArgs& a, int D, bool f16, hipStream_t st);
+// the combine pass of fa_decode alone: merges part_o / part_ml of a.nsplit splits into a.o / a.lse
+void fa_decode_combine(const DecArgs& a, int D, bool f16, hipStream_t st);
+// flash_chunk.hip: query chunks of any length over slab ranges (k_range) or a paged pool (block_table), bf16 / fp16 /
+// FP8 codes; 128 GQA-packed rows per workgroup.  k_range is required (cu_k is not read).  The plan depends on host
+// values only; splits > 0 forces that many (clipped to whole 64-key tiles).  nsplit > 1 needs part_o / part_ml.
+void fa_chunk_plan(int64_t max_q, int64_t max_k, int Hkv, int group, int nseg, bool paged, int splits, int& split_keys,
+                   int& nsplit);
+void fa_chunk(const DecArgs& a, int D, bool f16, int max_q, hipStream_t st);
 }
 
 struct BwdArgs {

@@ -99,6 +99,7 @@ _FILE_FLAGS: dict[str, list[str]] = {f: _NO_SLP for f in ("flash_fwd.hip", "flas
                                                            "xent_embed_optim.hip", "elementwise.hip")}
 # wide.hip: no packed-fp32 instructions at all (the staging arithmetic of its NORM prologue is fp32 on whole fragments,
 # which the backend would otherwise pack)
+_FILE_FLAGS["flash_chunk.hip"] = _NO_SLP  # the softmax loop of flash_fwd.hip: the same reasoning, not measured apart
 _FILE_FLAGS["wide.hip"] = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 

@@ -493,6 +493,20 @@ class PageAllocator:
         self._free.extend(reversed(list(pages)))
 
 
+class ChunkPass:
+    """One chunk of a chunked prefill, set on the shared ``PagedDecodeState`` while the chunk is forwarded: the
+    sequence owns ``pages``, the chunk's ``n`` tokens sit at positions ``start .. start + n - 1``.  Every attention
+    layer writes the chunk's K/V rows into the pages (``write_rows``) and attends with ``ops.attention.chunk_attention``
+    over the pool through ``table`` [1, max_pages] (the sequence's row of the block table) and ``k_range`` =
+    [[0, start + n]]."""
+
+    def __init__(self, pages: Sequence[int], start: int, n: int, table: torch.Tensor) -> None:
+        self.pages, self.start, self.n, self.table = list(pages), start, n, table
+        device = table.device
+        self.k_range = torch.tensor([[0, start + n]], dtype=torch.int32, device=device)
+        self.cu_q = torch.tensor([0, n], dtype=torch.int32, device=device)
+
+
 class PagedDecodeState(BatchDecodeState):
     """``BatchDecodeState`` of a paged KV cache, shared by every layer's ``PagedKVCache``; every tensor keeps its address
     for the life of the decoder, so a captured step sees admissions and page allocations as changed device values.
@@ -519,6 +533,7 @@ class PagedDecodeState(BatchDecodeState):
         self.block_table = torch.full((batch, max_pages), -1, dtype=torch.int32, device=device)
         self.live = torch.zeros(batch, dtype=torch.long, device=device)
         self.err = torch.zeros(1, dtype=torch.int32, device=device)
+        self.chunk: Optional[ChunkPass] = None  # set for the duration of a chunked-prefill forward
         for b in range(batch):
             self.park(b)
 
@@ -531,12 +546,17 @@ class PagedDecodeState(BatchDecodeState):
         self.k_range[b : b + 1, 1].fill_(1)
         self.live[b : b + 1].fill_(0)
 
-    def assign(self, b: int, pages: Sequence[int], n_prompt: int) -> None:
-        """Row b takes a request of ``n_prompt`` cached tokens in ``pages`` (device copies from fresh host tensors)."""
-        assert len(pages) <= self.max_pages and 0 <= n_prompt < len(pages) * self.page
+    def set_table(self, b: int, pages: Sequence[int]) -> None:
+        """Row b's table row names ``pages`` (a device copy from a fresh host tensor); position and length stay."""
+        assert len(pages) <= self.max_pages
         row = torch.full((self.max_pages,), -1, dtype=torch.int32)
         row[: len(pages)] = torch.tensor(list(pages), dtype=torch.int32)
         self.block_table[b].copy_(row)
+
+    def assign(self, b: int, pages: Sequence[int], n_prompt: int) -> None:
+        """Row b takes a request of ``n_prompt`` cached tokens in ``pages`` (device copies from fresh host tensors)."""
+        assert 0 <= n_prompt < len(pages) * self.page
+        self.set_table(b, pages)
         self.pos[b : b + 1].fill_(n_prompt)
         self.k_range[b : b + 1, 1].fill_(n_prompt + 1)
         self.live[b : b + 1].fill_(1)
@@ -610,6 +630,13 @@ class PagedKVCache(BatchStaticKVCache):
         self.k.index_copy_(0, rows, kv.k[: kv.length])
         self.v.index_copy_(0, rows, kv.v[: kv.length])
 
+    def write_rows(self, pages: Sequence[int], start: int, k: torch.Tensor, v: torch.Tensor) -> None:
+        """Writes ``k`` / ``v`` ``[n, nkv, hd]`` as logical rows ``start .. start + n - 1`` of a sequence that owns
+        ``pages`` (``load_row`` in pieces: a chunked prefill writes each chunk where it belongs)."""
+        rows = self.state.rows_of(pages, start + k.shape[0])[start:]
+        self.k.index_copy_(0, rows, k.to(self.k.dtype))
+        self.v.index_copy_(0, rows, v.to(self.v.dtype))
+
     def append(self, k: torch.Tensor, v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         st = self.state
         assert k.shape[0] == st.batch, "batched decoding feeds one token per sequence and step"
@@ -649,6 +676,17 @@ class PagedKVCacheFP8(_FP8Rows, PagedKVCache):
             q, s = quant_ops.quantize_kv_rows(src[: kv.length].to(torch.bfloat16))
             codes.index_copy_(0, rows, q)
             scale.index_copy_(1, rows, s)
+
+    def write_rows(self, pages: Sequence[int], start: int, k: torch.Tensor, v: torch.Tensor) -> None:
+        """``PagedKVCache.write_rows`` with the rows quantised as ``append`` does (non-finite values replaced, bit 1 of
+        the error word set): for finite rows the codes and scales are ``load_row``'s."""
+        rows = self.state.rows_of(pages, start + k.shape[0])[start:]
+        for codes, scale, x in ((self.k, self.k_scale, k), (self.v, self.v_scale, v)):
+            xb, nonfinite = quant_ops.sanitize_kv(x)
+            q, s = quant_ops.quantize_kv_rows(xb, check=False)
+            codes.index_copy_(0, rows, q)
+            scale.index_copy_(1, rows, s)
+            self.state.err.bitwise_or_(nonfinite.to(torch.int32) * 2)
 
     def append(self, k: torch.Tensor, v: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         st = self.state
@@ -876,6 +914,8 @@ class ParallelSelfAttention(torch.nn.Module):
         forward)."""
         if not use_cache or reset_cache:  # real decode steps only (see TransformerLayer.forward)
             return None
+        if self._chunk_pass(cache_index) is not None:  # a prefill chunk, however short: the unfused path
+            return None
         prologue = getattr(norm, "gemv_prologue", None)
         nw = prologue() if prologue is not None and _DECODE_FUSED else None
         if nw is None or x.dim() != 3 or not use_native(x) or not x.is_contiguous():
@@ -907,6 +947,24 @@ class ParallelSelfAttention(torch.nn.Module):
             return {"projected_step": step}
         _, base = decode_kernel(rows, "_norm")(x2, None, nw[0], nw[1], w, 0)
         return {"projected_base": base.view(*x.shape[:-1], w.shape[0])}
+
+    def _chunk_pass(self, cache_index: int) -> Optional[ChunkPass]:
+        """The chunked-prefill pass in progress on this layer's paged cache, if any (``ChunkPass``)."""
+        kv = self.cache.get(cache_index)
+        return kv.state.chunk if isinstance(kv, PagedKVCache) else None
+
+    def _chunk_attention(self, kv: PagedKVCache, chunk: ChunkPass, q: torch.Tensor, k: torch.Tensor,
+                         v: torch.Tensor) -> torch.Tensor:
+        """Chunk mode: the chunk's rotated k and v go into the sequence's pages, then its queries attend over the pool
+        (their own rows included) through the chunk's table."""
+        assert self.use_flash_attention and self.causal and q.shape[0] == chunk.n, "chunked prefill: flash, causal"
+        kv.write_rows(chunk.pages, chunk.start, k, v)
+        nl = self.num_local_attention_heads
+        return attn_ops.chunk_attention(
+            q, kv.k, kv.v, chunk.cu_q, chunk.k_range, chunk.n, chunk.start + chunk.n, self.scaling_factor, causal=True,
+            window=self.local_attention_window_size if nl > 0 else None,
+            local_heads=self.num_local_attention_heads_per_partition if nl > 0 else None,
+            kv_scales=_fp8_scales(kv), block_table=chunk.table, page_size=kv.state.page)
 
     def _decode_norm_rope_step(self, x2: torch.Tensor, nw: tuple, w: torch.Tensor, position_ids: Optional[torch.Tensor],
                                use_cache: bool, reset_cache: bool, cache_index: int) -> Optional[tuple]:
@@ -1018,6 +1076,22 @@ class ParallelSelfAttention(torch.nn.Module):
         p = next(self.parameters())
         _check_kv_dtype(p.dtype, p.is_cuda, "FP8 KV cache")
 
+    def check_chunked_prefill(self) -> None:
+        """Raises ``ValueError`` naming the restriction if this layer cannot take a chunked prefill into a paged cache
+        (``ContinuousBatchDecoder(prefill_chunk=...)``), before anything is allocated."""
+        if not self.use_flash_attention:
+            raise ValueError("chunked prefill: the torch (non-flash) attention kernel is not supported; set "
+                             "masked_softmax.kernel to 'flash_attention'")
+        if self.key_query_norm:
+            raise ValueError("chunked prefill: key_query_norm is not supported")
+        if self.topology is not None and self.topology.config.model_parallel_size > 1:
+            raise ValueError("chunked prefill: tensor parallelism (model_parallel_size > 1) is not supported")
+        if not self.causal:
+            raise ValueError("chunked prefill: causal attention only")
+        p = next(self.parameters())
+        if p.is_cuda and p.dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"chunked prefill: bfloat16 / float16 models only on the GPU (got {p.dtype})")
+
     def _decode_rope_append(self, base: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                             position_ids: Optional[torch.Tensor], cache_index: int) -> Optional[tuple]:
         """One-token step of graph-captured decoding: rotate q and k and append k/v at the cache's device-side
@@ -1106,6 +1180,9 @@ class ParallelSelfAttention(torch.nn.Module):
         batch_kv = self.cache.get(cache_index) if use_cache and not reset_cache else None
         if not isinstance(batch_kv, BatchStaticKVCache):
             batch_kv = None
+        # chunked prefill into a paged cache: x is [1, n, h], one sequence's chunk (no fused decode path applies)
+        chunk = batch_kv.state.chunk if isinstance(batch_kv, PagedKVCache) else None
+        assert chunk is None or (b == 1 and projected_step is None), "a prefill chunk is one sequence's tokens"
         # FP8 static cache (decode steps only): k / v below are its codes, read with these scales
         kv_scales = _fp8_scales(self.cache.get(cache_index)) if use_cache and not reset_cache else None
         probe("attention.input", x)
@@ -1135,7 +1212,7 @@ class ParallelSelfAttention(torch.nn.Module):
                 q = all_shard(self.norm_query(all_concat(q, dim=1, topology=self.topology)), dim=1, topology=self.topology)
                 k = all_shard(self.norm_key(all_concat(k, dim=1, topology=self.topology)), dim=1, topology=self.topology)
             if (use_cache and not reset_cache and (T == 1 or batch_kv is not None) and not self.key_query_norm
-                    and _DECODE_FUSED):
+                    and _DECODE_FUSED and chunk is None):
                 fused_append = self._decode_rope_append(base, q, k, v, position_ids, cache_index)
             if fused_append is not None:  # graph decode: RoPE + K/V cache append in one launch
                 q, k, v, cumulative_seq_lengths_key = fused_append
@@ -1144,6 +1221,8 @@ class ParallelSelfAttention(torch.nn.Module):
                 q = self.rotary_embedding.apply_tokens(q, pos, s)
                 k = self.rotary_embedding.apply_tokens(k, pos, s)
 
+        if chunk is not None:
+            return self._output(self._chunk_attention(batch_kv, chunk, q, k, v).reshape(b, s, -1))
         if use_cache and fused_append is None:
             if not self.causal:
                 raise ValueError("KV caching is only supported for causal attention.")

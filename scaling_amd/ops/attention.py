@@ -429,6 +429,68 @@ def _flash_attention_fp8_kv(q, k, v, kv_scales, cu_seqlens_q, cu_seqlens_k, key_
     return o
 
 
+def chunk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor,
+                    key_ranges: torch.Tensor, max_seqlen_q: int, max_seqlen_k: int,
+                    softmax_scale: Optional[float] = None, causal: bool = True, window: Optional[int] = None,
+                    local_heads: Optional[int] = None,
+                    kv_scales: Optional[tuple[torch.Tensor, torch.Tensor]] = None,
+                    block_table: Optional[torch.Tensor] = None, page_size: Optional[int] = None,
+                    splits: int = 0, return_lse: bool = False) -> Any:
+    """Attention of query chunks of ANY length over keys held in a KV cache (``csrc/kernels/flash_chunk.hip``): what a
+    chunked prefill, prefix reuse or a multi-token verification step needs and :func:`flash_attention` refuses above
+    ``32 / group`` queries.  Forward only (raises under grad).
+
+    q ``[T, Hq, D]`` with segments ``cu_seqlens_q``; segment i reads ``key_ranges[i] = (start, length)`` rows of the
+    slab buffers k / v ``[rows, Hk, D]`` or, with ``block_table`` int32 ``[nseg, max_pages]`` and ``page_size`` (a
+    multiple of 32), ``(0, length)`` keys of a pool of pages (key j = pool row ``block_table[i, j // page] * page +
+    j % page``; an entry outside the pool masks its keys, rows past the length are never read).  Causality is
+    bottom-right aligned (``key <= query + Lk - Lq``): a chunk of n tokens after ``ctx`` cached ones passes length
+    ``ctx + n``.  ``kv_scales`` = (k_scale, v_scale) float32 ``[Hk, rows]``: k / v are e4m3 codes (bfloat16 queries
+    only); the result equals the bf16 call on the dequantised K/V bit for bit, as the paged call equals the slab call
+    on the gathered rows.  ``max_seqlen_q`` / ``max_seqlen_k`` size the grid and the split plan (host values, no
+    read-back); ``splits`` > 0 forces a split count.  On CPU tensors the dense reference runs on the gathered,
+    dequantised keys.  GPU tensors require the extension."""
+    from .quant import dequantize_kv_rows
+
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise ValueError("chunk attention is forward only (run under torch.no_grad())")
+    if key_ranges is None:
+        raise ValueError("chunk attention: key_ranges ((start, length) per segment) are required")
+    paged = block_table is not None or page_size is not None
+    if paged:
+        page_size = _check_pages(q, k, cu_seqlens_q, key_ranges, block_table, page_size)
+    if kv_scales is not None:
+        if q.dtype == torch.float16:
+            raise ValueError("chunk attention: FP8 K/V (kv_scales) needs bfloat16 queries, got torch.float16")
+        for t, sc in ((k, kv_scales[0]), (v, kv_scales[1])):
+            if t.dtype not in (torch.uint8, torch.float8_e4m3fn):
+                raise ValueError(f"chunk attention: with kv_scales, k and v must be uint8 / float8_e4m3fn codes, got {t.dtype}")
+            if sc.dtype != torch.float32 or tuple(sc.shape) != (t.shape[1], t.shape[0]):
+                raise ValueError(f"chunk attention: kv_scales must be float32 [kv heads, key rows] = "
+                                 f"{(t.shape[1], t.shape[0])}, got {sc.dtype} {tuple(sc.shape)}")
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    win = -1 if window is None else int(window)
+    if not use_native(q):
+        ks, vs = kv_scales if kv_scales is not None else (None, None)
+        if paged:
+            rows, key_ranges = gather_pages(block_table, page_size, key_ranges[:, 1].tolist())
+            k, v = k.index_select(0, rows), v.index_select(0, rows)
+            if ks is not None:
+                ks, vs = ks.index_select(1, rows), vs.index_select(1, rows)
+        if ks is not None:
+            k, v = dequantize_kv_rows(k, ks, q.dtype), dequantize_kv_rows(v, vs, q.dtype)
+        out = attention_reference(q, k, v, cu_seqlens_q, None, scale, causal, win, local_heads=local_heads,
+                                  key_ranges=key_ranges)
+        return (out, None) if return_lse else out
+    if q.dtype not in (torch.bfloat16, torch.float16) or (kv_scales is not None and q.dtype != torch.bfloat16):
+        raise ValueError(f"chunk attention supports bfloat16 / float16 queries (bfloat16 with kv_scales), got {q.dtype}")
+    ks, vs = kv_scales if kv_scales is not None else (None, None)
+    o, lse = ext().fa_chunk(q, k, v, cu_seqlens_q.to(torch.int32), int(max_seqlen_q), float(scale), bool(causal), win,
+                            -1 if local_heads is None else int(local_heads), int(max_seqlen_k), key_ranges, ks, vs,
+                            block_table, int(page_size) if paged else 0, int(splits))
+    return (o, lse) if return_lse else o
+
+
 def flash_attention(
     q: torch.Tensor,
     k: torch.Tensor,

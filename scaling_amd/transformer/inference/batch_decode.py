@@ -46,8 +46,8 @@ from typing import Any, Callable, Optional, Sequence
 import torch
 
 from ...ops import gemm as gemm_ops
-from ...core.nn.attention.attention import (BatchDecodeState, BatchStaticKVCache, BatchStaticKVCacheFP8, KVCache,
-                                            PageAllocator, PagedDecodeState, PagedKVCache, PagedKVCacheFP8,
+from ...core.nn.attention.attention import (BatchDecodeState, BatchStaticKVCache, BatchStaticKVCacheFP8, ChunkPass,
+                                            KVCache, PageAllocator, PagedDecodeState, PagedKVCache, PagedKVCacheFP8,
                                             ParallelSelfAttention, check_kv_cache_scheme, check_page_size)
 from ..data import TextDatasetBatch
 from ..data.inference_settings import InferenceSettings
@@ -252,16 +252,31 @@ class ContinuousBatchDecoder:
     ``[R, B, V]``); ``serve`` reads it back once per ``check_every <= record_steps`` steps and files the rows' entries
     under their requests.
 
-    Not here: preemption or swapping when the pool is full (``admit`` / ``step`` raise), prefix sharing, paged or
-    batched prefill (a prompt is prefilled alone by the existing eager path and copied into its pages)."""
+    ``prefill_chunk=C`` (opt-in, a positive multiple of 32; bf16 / fp16 models on one device, flash attention, no
+    ``key_query_norm``): ``admit`` forwards the prompt in chunks of at most ``C`` tokens straight into its freshly
+    allocated pages -- every layer writes the chunk's K/V rows (``PagedKVCache.write_rows``) and attends over the pool
+    with ``ops.attention.chunk_attention`` (``csrc/kernels/flash_chunk.hip``) --, so no contiguous copy of the prompt's
+    K/V, no spare cache index and no ``load_row``; activations are those of one chunk.  The captured step is not
+    touched (``captures`` stays 1).  With ``kv_cache="fp8_e4m3"`` the later chunks read the earlier chunks' keys as e4m3
+    codes: the prompt's own prefill then sees quantised K/V, which the unchunked admit (prefill against exact bf16
+    K/V, quantised afterwards) does not.  Chunks at or below ``ops.gemm.decode_rows_limit()`` rows may run their
+    linear layers on the decode kernels.  ``None`` (default) is the unchunked path, unchanged.
+
+    Not here: preemption or swapping when the pool is full (``admit`` / ``step`` raise), prefix sharing, batched
+    prefill (a prompt is prefilled alone), prefill chunks interleaved with decode steps inside the captured step."""
 
     def __init__(self, module: Any, max_batch: int, page_size: int = 64, max_pages: int = 1,
                  num_pages: Optional[int] = None, sample_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
                  skinny_gemm: bool = False, kv_cache: Optional[str] = None, use_cuda_graph: bool = False,
-                 record_steps: int = 8, wide_batch: bool = False) -> None:
+                 record_steps: int = 8, wide_batch: bool = False, prefill_chunk: Optional[int] = None) -> None:
         from .sample import sample_argmax
 
         self.module = module
+        if prefill_chunk is not None and (not isinstance(prefill_chunk, int) or isinstance(prefill_chunk, bool)
+                                          or prefill_chunk <= 0 or prefill_chunk % 32):
+            raise ValueError(f"ContinuousBatchDecoder: prefill_chunk must be a positive multiple of 32, got "
+                             f"{prefill_chunk!r}")
+        self.prefill_chunk = prefill_chunk
         self.wide_batch = bool(wide_batch)
         self.skinny_gemm = bool(skinny_gemm) or self.wide_batch
         self.kv_cache = check_kv_cache_scheme(kv_cache, "ContinuousBatchDecoder")
@@ -282,6 +297,9 @@ class ContinuousBatchDecoder:
         if self.kv_cache is not None:
             for a in self.attns:
                 a.check_fp8_kv_cache()
+        if prefill_chunk is not None:
+            for a in self.attns:
+                a.check_chunked_prefill()
         p0 = next(self.attns[0].parameters())
         dev = p0.device
         self.batch_size, self.page_size, self.max_pages = B, page, int(max_pages)
@@ -381,6 +399,8 @@ class ContinuousBatchDecoder:
         if self.rows[row] is not None:
             raise ValueError(f"ContinuousBatchDecoder.admit: row {row} holds a request (release it first)")
         pages = self.allocator.alloc(-(-(n + 1) // self.page_size))  # RuntimeError before anything is written
+        if self.prefill_chunk is not None:
+            return self._admit_chunked(row, list(input_tokens), int(max_tokens), index, pages)
         settings = InferenceSettings(use_cache=True, reset_cache=True, cache_index=self.spare_index, embedding_layers=[-1])
         with torch.no_grad():
             try:
@@ -398,6 +418,40 @@ class ContinuousBatchDecoder:
             self.state.assign(row, pages, n)
             self.tok[row : row + 1].copy_(first)
         req = _Request(index, n, int(max_tokens), pages)
+        req.tokens.append(int(first.item()))
+        req.logits.append(last.reshape(1, -1))
+        self.rows[row] = req
+        return req
+
+    def _admit_chunked(self, row: int, tokens: list[int], max_tokens: int, index: Any, pages: list[int]) -> _Request:
+        """``admit`` with ``prefill_chunk``: the prompt goes through the model in chunks that write their K/V straight
+        into ``pages`` and attend over the pool (``ChunkPass``).  The row stays parked until the last chunk is in, so the
+        captured step's rows are not disturbed; the row's table row is written before the first chunk."""
+        n, C, st = len(tokens), self.prefill_chunk, self.state
+        dev = st.pos.device
+        settings = InferenceSettings(use_cache=True, reset_cache=False, cache_index=0, embedding_layers=[-1])
+        ids = torch.tensor(tokens, dtype=torch.long, device=dev).unsqueeze(0)
+        with torch.no_grad():
+            try:
+                st.set_table(row, pages)  # the row itself stays parked at position 0 until assign() below
+                for start in range(0, n, C):
+                    m = min(C, n - start)
+                    st.chunk = ChunkPass(pages, start, m, st.block_table[row : row + 1])
+                    pos = torch.arange(start, start + m, dtype=torch.long, device=dev).unsqueeze(0)
+                    with gemm_ops.skinny_gemm(self.skinny_gemm, wide=self.wide_batch):
+                        out = self.module.forward(TextDatasetBatch(input_token_ids=ids[:, start : start + m],
+                                                                   position_ids=pos, inference_settings=settings))
+            except BaseException:
+                st.park(row)
+                self.allocator.free(pages)
+                raise
+            finally:
+                st.chunk = None
+            last = out.activations[:, -1:, :]
+            first = self.sample_fn(last).reshape(1, 1).to(torch.long)
+            st.assign(row, pages, n)
+            self.tok[row : row + 1].copy_(first)
+        req = _Request(index, n, max_tokens, pages)
         req.tokens.append(int(first.item()))
         req.logits.append(last.reshape(1, -1))
         self.rows[row] = req

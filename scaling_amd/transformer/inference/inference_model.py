@@ -391,7 +391,8 @@ class TransformerInferenceModule(InferenceModule):
                            num_pages: Optional[int] = None,
                            sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                            use_cuda_graph: bool = False, skinny_gemm: bool = False,
-                           kv_cache: Optional[str] = None, record_steps: int = 8, wide_batch: bool = False) -> Any:
+                           kv_cache: Optional[str] = None, record_steps: int = 8, wide_batch: bool = False,
+                           prefill_chunk: Optional[int] = None) -> Any:
         """The ``batch_decode.ContinuousBatchDecoder`` of this model for a serving loop (``admit`` / ``step`` /
         ``release``, or ``serve``): ``max_batch`` rows over a paged KV cache whose requests take at most ``max_pages``
         pages of ``page_size`` tokens; captured once when ``use_cuda_graph``.  See ``generate_continuous``."""
@@ -401,7 +402,8 @@ class TransformerInferenceModule(InferenceModule):
             raise RuntimeError("generate_continuous: the model must sit on one device")
         return ContinuousBatchDecoder(self, max_batch, page_size=page_size, max_pages=max_pages, num_pages=num_pages,
                                       sample_fn=sample_fn, skinny_gemm=skinny_gemm, kv_cache=kv_cache,
-                                      use_cuda_graph=use_cuda_graph, record_steps=record_steps, wide_batch=wide_batch)
+                                      use_cuda_graph=use_cuda_graph, record_steps=record_steps, wide_batch=wide_batch,
+                                      prefill_chunk=prefill_chunk)
 
     def generate_continuous(self, max_tokens: Any, input_texts: Optional[Sequence[str]] = None,
                             input_tokens: Optional[Sequence[Sequence[int]]] = None, max_batch: int = 4,
@@ -409,7 +411,7 @@ class TransformerInferenceModule(InferenceModule):
                             sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
                             stop_tokens: Optional[Sequence[int]] = None, use_cuda_graph: bool = False,
                             skinny_gemm: bool = False, kv_cache: Optional[str] = None,
-                            wide_batch: bool = False) -> list[CompletionOutput]:
+                            wide_batch: bool = False, prefill_chunk: Optional[int] = None) -> list[CompletionOutput]:
         """Completions for N requests (N may exceed ``max_batch``) by continuous batching over a paged KV cache:
         ``max_batch`` rows share every decode step, and a row whose request reaches a stop token or its own
         ``max_tokens`` (an int, or one int per request) is refilled with the next request while the others go on
@@ -421,7 +423,11 @@ class TransformerInferenceModule(InferenceModule):
         ``RuntimeError`` when it runs out (there is no preemption).  ``use_cuda_graph`` captures the step once for the
         whole stream and has ``generate_batch``'s limits on ``max_batch`` (4, 16 with ``skinny_gemm``, 64 with
         ``wide_batch``); ``kv_cache`` as in ``generate_batch``.  Greedy completions equal ``generate``'s per prompt up to the rounding of the batched
-        kernels; with a seeded ``Sampler`` a draw depends on the row and the step a request happens to occupy."""
+        kernels; with a seeded ``Sampler`` a draw depends on the row and the step a request happens to occupy.
+
+        ``prefill_chunk=C`` (a positive multiple of 32, else ``ValueError``): every prompt is prefilled in chunks of at
+        most ``C`` tokens straight into its pages (``ContinuousBatchDecoder``); with an FP8 KV cache the prompt's later
+        chunks then read its earlier keys as e4m3 codes.  ``None`` is the unchunked prefill."""
         if (input_texts is None) == (input_tokens is None):
             raise ValueError("generate_continuous: give either input_texts or input_tokens")
         if input_texts is not None:
@@ -444,7 +450,8 @@ class TransformerInferenceModule(InferenceModule):
         longest = max(len(p) + m for p, m in zip(input_tokens, limits))
         dec = self.continuous_decoder(max_batch, page_size=page_size, max_pages=-(-longest // page_size),
                                       num_pages=num_pages, sample_fn=sample_fn, use_cuda_graph=use_cuda_graph,
-                                      skinny_gemm=skinny_gemm, kv_cache=kv_cache, wide_batch=wide_batch)
+                                      skinny_gemm=skinny_gemm, kv_cache=kv_cache, wide_batch=wide_batch,
+                                      prefill_chunk=prefill_chunk)
         outs = []
         for tokens, logits in dec.serve(list(zip(input_tokens, limits)), stop_tokens):
             text = self.tokenizer.decode(tokens) if self.tokenizer is not None else None

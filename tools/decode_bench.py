@@ -2,7 +2,7 @@
 
     python tools/decode_bench.py [--model llama2_7b] [--prompt 128] [--tokens 64] [--sampler T,K,P | torch:T,K,P]
                                  [--weights fp8_e4m3 | mxfp4 | bf16,fp8_e4m3,mxfp4 [--lm-head]] [--batch B [--skinny | --wide]]
-                                 [--kv-cache bf16,fp8_e4m3 [--rounds N]] [--paged 0,64] [--continuous N]
+                                 [--kv-cache bf16,fp8_e4m3 [--rounds N]] [--paged 0,64] [--continuous N [--prefill-chunk 0,512,2048]]
 
 ``--batch B`` times batched generation instead (``generate_batch`` / ``BatchDecoder``): B random prompts of lengths
 ``prompt, prompt - 7, prompt - 14, ...`` decoded together; ms per step, tokens/s summed over the rows, and (B <= 4:
@@ -31,6 +31,8 @@ over the paged cache (``ContinuousBatchDecoder.serve``, page size ``--paged`` or
 comparison, by ``batch_decoder`` over the same requests in arrival-order groups of B, each group running to its longest
 ``max_tokens``.  Wall time covers prefills and decoding of both (graph captures excluded); tokens are the requested ones.
 Also prints the KV memory each held: pages in use at the peak x bytes per page against B slabs of ``cap`` rows.
+``--prefill-chunk 0,512,2048`` (with ``--continuous``) measures admission instead: one ``admit`` of a ``--prompt``-token
+prompt per setting (0: the unchunked admit), wall time and peak allocated memory above the decoder's own.
 
 ``--sampler 0.8,40,0.95`` decodes with the fused ``Sampler`` (temperature, top-k, top-p) in both loops;
 ``--sampler torch:0.8,40,0.95`` times the eager loop with the torch composition
@@ -74,6 +76,9 @@ def main() -> None:
     p.add_argument("--continuous", type=int, default=0, help="with --batch B --skinny: serve N requests by continuous "
                    "batching and by static groups of B")
     p.add_argument("--spread", default="32,256", help="with --continuous: range of the requests' max_tokens")
+    p.add_argument("--prefill-chunk", default="", help="with --continuous: comma list of prefill_chunk settings (0: the "
+                   "unchunked admit); instead of the request stream, times ONE admit of a --prompt-token prompt per "
+                   "setting (--rounds times, alternating): wall time and peak allocated memory over the admission")
     a = p.parse_args()
     a.page_list = [int(x) or None for x in a.paged.split(",")]
     a.kv_list = [None if k == "bf16" else k for k in a.kv_cache.split(",")]
@@ -207,6 +212,8 @@ def continuous_bench(m, a, arch, sample_fn, timed, kv=None) -> None:
     per_token = arch.num_layers * 2 * nkv * (2 * hd if kv is None else hd + 4)
     kw = dict(skinny_gemm=a.skinny, kv_cache=kv, wide_batch=a.wide)
     graph = next(m.parameters()).is_cuda
+    if a.prefill_chunk:
+        return admit_bench(m, a, arch, timed, kv, page, reqs[0][0], kw)
     longest = max(len(p) + mt for p, mt in reqs)
     m.generate_continuous(4, input_tokens=[p for p, _ in reqs[:B]], max_batch=B, page_size=page, stop_tokens=[],
                           use_cuda_graph=graph, sample_fn=sample_fn, **kw)  # warm-up
@@ -236,6 +243,27 @@ def continuous_bench(m, a, arch, sample_fn, timed, kv=None) -> None:
         "continuous_kv_gib": round((dec.allocator.peak_in_use + B) * page * per_token / 2**30, 3),
         "static_kv_rows": cap_rows, "static_kv_gib": round(cap_rows * per_token / 2**30, 3),
     }), flush=True)
+
+
+def admit_bench(m, a, arch, timed, kv, page, prompt, kw) -> None:
+    """``--continuous N --prefill-chunk 0,512,...``: one admission of ``prompt`` per setting (after one warm-up admission
+    of the same prompt): wall time, and the peak of allocated memory above what was allocated before the admission."""
+    for c in (int(x) for x in a.prefill_chunk.split(",")):
+        dec = m.continuous_decoder(a.batch, page_size=page, max_pages=-(-(len(prompt) + 2) // page),
+                                   prefill_chunk=c or None, **kw)
+        dec.admit(0, prompt, 1)
+        dec.release(0)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        t, _ = timed(lambda: dec.admit(0, prompt, 1))
+        print(json.dumps({
+            "metric": "admission of one prompt, continuous decoder", "model": a.model, "layers": arch.num_layers,
+            "prompt": len(prompt), "page": page, "kv_cache": kv or "bf16", "prefill_chunk": c or None,
+            "admit_ms": round(1e3 * t, 2), "peak_above_start_mib": round((torch.cuda.max_memory_allocated() - before) / 2**20, 1),
+            "allocated_at_start_mib": round(before / 2**20, 1),
+        }), flush=True)
+        del dec
 
 
 def batch_bench(m, a, arch, sample_fn, mode, timed, quantised, kv=None, page=None) -> None:
