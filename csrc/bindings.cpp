@@ -738,6 +738,60 @@ SA_W4_ENTRY(gemv, kGemv)
 SA_W4_ENTRY(skinny, kSkinny)
 SA_W4_ENTRY(wide, kWide)
 #undef SA_W4_ENTRY
+// Prefill GEMM over the quantised copies (qgemm.hip): the operand rules of the _w8 / _w4 decode entry points without
+// the row limit; out (optional) a contiguous bf16 [M, N] on x's device, or any contiguous bf16 tensor of M * N elements
+// whose last dimension is N (the un-flattened output).  Launches on the current stream, reads no device value.
+bool qgemm_operands_ok(const at::Tensor& x, const at::Tensor& W, const at::Tensor& scale) {
+    if (!(x.is_cuda() && x.dim() == 2 && x.size(0) >= 1)) return false;
+    // (the decode rule with its row limit lifted: test the first row alone, then the row stride)
+    if (!gemv_operands_ok(x.narrow(0, 0, 1), W, &scale, kGemv)) return false;
+    return (x.size(0) == 1 || x.stride(0) % 8 == 0) && x.size(0) <= INT32_MAX && (W.size(0) + 127) / 128 <= 65535;
+}
+at::Tensor qgemm_impl(const char* name, const at::Tensor& x, const at::Tensor& W, const at::Tensor& scale,
+                      const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& out) {
+    TORCH_CHECK(qgemm_operands_ok(x, W, scale), name, ": unsupported operands ",
+                scale.dim() == 2 ? "(x bf16 [M, K], codes uint8 [N, K / 2] in whole rows, scales uint8 [N, K / 32] contiguous, K % 32 == 0)"
+                                 : "(x bf16 [M, K], Q e4m3fn [N, K], scale fp32 [N], K % 16 == 0, 16-byte aligned rows)");
+    const at::DeviceGuard g(x.device());
+    const int64_t M = x.size(0), N = W.size(0), K = x.size(1);
+    const void* bp = nullptr;
+    at::Tensor bc;
+    if (bias.has_value() && bias->defined()) {
+        TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() && bias->numel() == N &&
+                        bias->scalar_type() == x.scalar_type(), name, ": bias must be bf16 [N] on x's device");
+        bc = bias->contiguous();
+        bp = bc.data_ptr();
+    }
+    at::Tensor y;
+    if (out.has_value() && out->defined()) {
+        TORCH_CHECK(out->is_cuda() && out->device() == x.device() && out->scalar_type() == x.scalar_type() &&
+                        out->is_contiguous() && out->dim() >= 1 && out->size(-1) == N && out->numel() == M * N &&
+                        (uintptr_t)out->data_ptr() % 8 == 0, name, ": out must be a contiguous bf16 [M, N] on x's device");
+        y = *out;
+    } else {
+        y = at::empty({M, N}, x.options());
+    }
+    sa_launch::qgemm((int)M, x.data_ptr(), x.stride(0), W.data_ptr(), W.stride(0), scale_ptr(&scale), bscale_ptr(&scale),
+                     bp, y.data_ptr(), (int)N, (int)K, cur_stream());
+    return y;
+}
+bool qgemm_w8_ok(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale) {
+    return scale.dim() == 1 && qgemm_operands_ok(x, Q, scale);
+}
+at::Tensor qgemm_w8(const at::Tensor& x, const at::Tensor& Q, const at::Tensor& scale, c10::optional<at::Tensor> bias,
+                    c10::optional<at::Tensor> out) {
+    TORCH_CHECK(scale.dim() == 1, "qgemm_w8: scale must be one fp32 per row [N]");
+    return qgemm_impl("qgemm_w8", x, Q, scale, bias, out);
+}
+bool qgemm_w4_ok(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S) {
+    return S.dim() == 2 && qgemm_operands_ok(x, C, S);
+}
+at::Tensor qgemm_w4(const at::Tensor& x, const at::Tensor& C, const at::Tensor& S, c10::optional<at::Tensor> bias,
+                    c10::optional<at::Tensor> out) {
+    TORCH_CHECK(S.dim() == 2, "qgemm_w4: scales must be [N, K / 32]");
+    return qgemm_impl("qgemm_w4", x, C, S, bias, out);
+}
+
 void gemv_w4_rule(int64_t rpw, int64_t ks) {
     TORCH_CHECK((rpw == 0 && ks == 0) || ((rpw == 1 || rpw == 2 || rpw == 4) && (ks == 1 || ks == 4)), "gemv_w4_rule");
     sa_launch::gemv_w4_rule((int)rpw, (int)ks);
@@ -1290,6 +1344,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("wide_w8_norm_ok", &wide_w8_norm_ok, "whether wide_w8_norm supports these operands");
     m.def("wide_w8_norm", &wide_w8_norm, "(s, wide_w8(rms_norm(s), Q, scale)) with s = x (+ add); epi 0 plain, 2 SwiGLU",
           py::arg("x"), py::arg("add"), py::arg("gamma"), py::arg("eps"), py::arg("q"), py::arg("scale"), py::arg("epi") = 0);
+    m.def("qgemm_w8_ok", &qgemm_w8_ok, "whether the FP8-weight prefill GEMM supports these operands");
+    m.def("qgemm_w8", &qgemm_w8, "y = x (scale * Q)^T (+ b) for any number of bf16 rows of x, Q e4m3fn codes, scale fp32 per row",
+          py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("bias") = py::none(), py::arg("out") = py::none());
+    m.def("qgemm_w4_ok", &qgemm_w4_ok, "whether the MXFP4-weight prefill GEMM supports these operands");
+    m.def("qgemm_w4", &qgemm_w4, "y = x deq(codes, scales)^T (+ b) for any number of bf16 rows of x, MXFP4 weights",
+          py::arg("x"), py::arg("codes"), py::arg("scales"), py::arg("bias") = py::none(), py::arg("out") = py::none());
     m.def("gemv_w4_rule", &gemv_w4_rule, "A/B switch of tools/gemv_bench.py: force the MXFP4 GEMV's (rows per wave, waves per row); (0, 0) restores its rules");
     m.def("skinny_ok", &skinny_ok, "whether skinny supports these operands");
     m.def("skinny", &skinny, "y = x W^T (+ b) for at most 16 rows of x on the MFMA weight-streaming kernel (batched decode)",

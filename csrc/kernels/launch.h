@@ -225,4 +225,10 @@ void wide(int dtype, int M, const void* x, int64_t ldx, const void* W, int64_t l
           void* y, int64_t ldy, int N, int K, hipStream_t st, int epi = 0, const void* res = nullptr, int64_t ldr = 0,
           const void* norm_w = nullptr, const void* norm_add = nullptr, void* norm_sum = nullptr, float eps = 0.f,
           const uint8_t* bscale = nullptr, float* ws = nullptr);
+// qgemm.hip: y[M, N] = x[M, K] deq(W)[N, K]^T (+ b) over the quantised copies for ANY M >= 1 (the prefill GEMM): x bf16
+// with rows ldx apart, y bf16 contiguous [M, N]; scale != nullptr: FP8 (W e4m3fn codes, rows ldw bytes apart, K % 16 ==
+// 0); bscale != nullptr: MXFP4 (W e2m1 codes, rows ldw = K / 2 bytes apart, bscale [N, K / 32] e8m0, K % 32 == 0).  No
+// workspace, no split-K: bitwise deterministic.  Rows >= M of x are never read.
+void qgemm(int M, const void* x, int64_t ldx, const void* W, int64_t ldw, const float* scale, const uint8_t* bscale,
+           const void* bias, void* y, int N, int K, hipStream_t st);
 }  // namespace sa_launch

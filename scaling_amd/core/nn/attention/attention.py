@@ -934,7 +934,8 @@ class ParallelSelfAttention(torch.nn.Module):
             return None
         w = weights[0] if len(weights) == 1 else adjacent_weights(weights)
         x2 = x.reshape(rows, K)
-        if w is None or not decode_kernel(rows, "_norm_ok")(x2, w, nw[0]):
+        released = w is not None and quant_ops.released_name(w) is not None  # (no bf16 operand to test or to fall back on)
+        if w is None or not (released or decode_kernel(rows, "_norm_ok")(x2, w, nw[0])):
             return None
         wq = adjacent_wq(weights)  # (suffix, copy, scales) of either quantised format
         if wq is not None and decode_kernel(rows, wq[0] + "_norm_ok")(x2, wq[1], wq[2], nw[0]):
@@ -942,6 +943,8 @@ class ParallelSelfAttention(torch.nn.Module):
             # no FP8 or MXFP4 form, so RoPE + K/V append follow as their own launch (_decode_rope_append)
             _, base = decode_kernel(rows, wq[0] + "_norm")(x2, None, nw[0], nw[1], wq[1], wq[2], 0)
             return {"projected_base": base.view(*x.shape[:-1], w.shape[0])}
+        if released:
+            return None  # the unfused path: ops.gemm.linear serves a released weight, or raises naming it
         step = self._decode_norm_rope_step(x2, nw, w, position_ids, use_cache, reset_cache, cache_index)
         if step is not None:
             return {"projected_step": step}
@@ -1325,6 +1328,10 @@ class ParallelSelfAttention(torch.nn.Module):
     @torch.no_grad()
     def merge_lora_weights(self) -> None:
         assert self.lora_config and self.lora_modules, "Merge of LoRa weights called without proper configuration."
+        for n, p in self.named_parameters():
+            if quant_ops.released_name(p) is not None:
+                raise RuntimeError(f"merge_lora_weights: the bf16 weights of {n} were released "
+                                   "(quantize_weights(release_dense=True)); there is nothing to merge into")
         if self.qkv_in_one:
             keys = {f"{m.value}_{self.lora_config.name}" for m in (LoRAModuleType.KEY, LoRAModuleType.VALUE, LoRAModuleType.QUERY)}
             if keys.intersection(self.lora_modules.keys()):

@@ -51,9 +51,10 @@ import torch.distributed as dist
 
 from ....ops.attention import stash_gemm
 from ....ops.gemm import linear as gemm_linear
-from ....ops.gemm import decode_rows_limit, mm, mm_nt, transpose2d, wgrad
+from ....ops.gemm import check_no_graph, decode_rows_limit, mm, mm_nt, transpose2d, wgrad
 from ....ops.quant import adjacent_w8 as _adjacent_w8
 from ....ops.quant import adjacent_wq as _adjacent_wq
+from ....ops.quant import released_group, released_name
 from ...utils.debug_env import side_streams_enabled
 
 _GEN = [0]
@@ -131,6 +132,8 @@ def _adjacent(ts: Sequence[Optional[torch.Tensor]]) -> Optional[torch.Tensor]:
         return None
     first = ts[0]
     assert first is not None
+    if released_name(first) is not None:  # no bf16 values left to view: the group's released stand-in
+        return released_group(ts)  # type: ignore[arg-type]
     if len(ts) == 1:
         return first if first.is_contiguous() else None
     K = first.shape[-1]
@@ -244,7 +247,7 @@ class _MultiLinear(torch.autograd.Function):
                 *params: Optional[torch.Tensor]) -> torch.Tensor:
         weights = params[:n]
         biases = params[n:]
-        w = _adjacent(weights)
+        w = _adjacent(weights)  # (a released group: its stand-in, never None, so nothing is concatenated)
         if w is None:
             w = torch.cat(weights, dim=0)  # type: ignore[arg-type]
         has_bias = len(biases) > 0 and biases[0] is not None
@@ -253,7 +256,9 @@ class _MultiLinear(torch.autograd.Function):
             b = biases[0] if n == 1 else torch.cat(biases, dim=0)  # type: ignore[arg-type]
         # decode-sized rows of quantised weights stream the copy (w itself may be a fresh view over the group)
         K = x.shape[-1]
-        wq = adjacent_wq(weights) if K and 0 < x.numel() // K <= decode_rows_limit() else None  # type: ignore[arg-type]
+        # (a released group has nothing else: its copy is looked up for every row count)
+        wq = (adjacent_wq(weights)  # type: ignore[arg-type]
+              if K and (0 < x.numel() // K <= decode_rows_limit() or released_name(w) is not None) else None)
         out = stash_gemm(lambda: gemm_linear(x, w, b, wq=wq))
         wt = _transposed(weights, w) if want_wt else None
         ctx.has_wt = wt is not None
@@ -292,6 +297,8 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
            ) -> torch.Tensor:
     """``F.linear`` with GEMM-fused gradient accumulation for main-grad weights; ``tp_group``: all-reduce the
     input gradient over it (column-parallel weight, identity forward), overlapped with the wgrad GEMM."""
+    if released_name(weight) is not None:  # (the Function's forward runs with grad mode off: test here)
+        check_no_graph(released_name(weight), x, weight, bias)
     want_wt = torch.is_grad_enabled() and x.requires_grad
     if bias is None:
         return _MultiLinear.apply(x, 1, want_wt, tp_group, weight)
@@ -301,7 +308,9 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] =
 def multi_linear(x: torch.Tensor, weights: Sequence[torch.Tensor], biases: Optional[Sequence[Optional[torch.Tensor]]] = None,
                  tp_group: Any = None) -> torch.Tensor:
     """``x @ [W_1; ...; W_n]^T (+ [b_1; ...; b_n])`` as one GEMM (forward, dgrad and wgrad)."""
-    if len(weights) > 1 and _adjacent(weights) is None:
+    if released_name(weights[0]) is not None:
+        check_no_graph(released_name(weights[0]), x, *weights, *(biases or ()))
+    elif len(weights) > 1 and _adjacent(weights) is None:
         _rehome_adjacent(weights)
     want_wt = torch.is_grad_enabled() and x.requires_grad
     if biases is None or any(b is None for b in biases):

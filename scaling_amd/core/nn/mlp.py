@@ -18,6 +18,7 @@ import torch
 from ...ops import swiglu as swiglu_ops
 from ...ops._ext import ext, use_native
 from ...ops.gemm import decode_kernel, decode_rows_limit
+from ...ops.quant import released_name
 from ..topology import Topology
 from .activation_function import ActivationFunction, get_activation_function
 from .linear import ColumnParallelLinear, RowParallelLinear
@@ -112,8 +113,12 @@ class ParallelSwiGLUMLP(torch.nn.Module):
             return None
         w = adjacent_weights([self.dense_in.weight, self.siglu_weight.weight])
         wo = self.dense_out.weight
-        if (w is None or not decode_kernel(rows, "_ok")(x.reshape(rows, K), w) or wo.dtype != w.dtype or wo.stride(1) != 1
-                or wo.stride(0) % 8 or wo.shape[1] != w.shape[0] // 2 or wo.shape[1] % 8 or wo.data_ptr() % 16):
+        # a released weight (ops/quant.py) has no bf16 layout to test: its quantised copy's own ``_ok`` decides below
+        if w is None or wo.dtype != w.dtype or wo.shape[1] != w.shape[0] // 2 or wo.shape[1] % 8:
+            return None
+        if released_name(w) is None and not decode_kernel(rows, "_ok")(x.reshape(rows, K), w):
+            return None
+        if released_name(wo) is None and (wo.stride(1) != 1 or wo.stride(0) % 8 or wo.data_ptr() % 16):
             return None
         return w, wo
 
@@ -128,6 +133,9 @@ class ParallelSwiGLUMLP(torch.nn.Module):
         rows = a.shape[0]
         if woq is not None and decode_kernel(rows, woq[0] + "_ok")(a, woq[1], woq[2]):
             return decode_kernel(rows, woq[0] + "_residual")(a, woq[1], woq[2], res)
+        if released_name(wo) is not None:
+            raise RuntimeError(f"{released_name(wo)}: its bf16 weights were released and no quantised decode kernel "
+                               f"takes this call ({rows} rows)")
         return decode_kernel(rows, "_residual")(a, wo, res)
 
     def decode_forward_residual(self, x: torch.Tensor, residual: torch.Tensor) -> Optional[torch.Tensor]:
@@ -142,6 +150,8 @@ class ParallelSwiGLUMLP(torch.nn.Module):
         wq, woq = self._decode_wq()
         if wq is not None and decode_kernel(rows, wq[0] + "_ok")(x2, wq[1], wq[2]):
             h = decode_kernel(rows, wq[0] + "_swiglu")(x2, wq[1], wq[2])
+        elif released_name(ws[0]) is not None:
+            return None  # the unfused path: ops.gemm.linear serves a released weight, or raises naming it
         else:
             h = decode_kernel(rows, "_swiglu")(x2, ws[0])
         return self._down_residual(h, ws[1], woq, residual.reshape(rows, -1)).view(residual.shape)
@@ -162,11 +172,13 @@ class ParallelSwiGLUMLP(torch.nn.Module):
             return None
         rows = h.numel() // h.shape[-1]
         h2 = h.reshape(rows, -1)
-        if not decode_kernel(rows, "_norm_ok")(h2, ws[0], nw[0]):
+        if released_name(ws[0]) is None and not decode_kernel(rows, "_norm_ok")(h2, ws[0], nw[0]):
             return None
         wq, woq = self._decode_wq()
         if wq is not None and decode_kernel(rows, wq[0] + "_norm_ok")(h2, wq[1], wq[2], nw[0]):
             s, a = decode_kernel(rows, wq[0] + "_norm")(h2, residual.reshape(rows, -1), nw[0], nw[1], wq[1], wq[2], 2)
+        elif released_name(ws[0]) is not None:
+            return None
         else:
             s, a = decode_kernel(rows, "_norm")(h2, residual.reshape(rows, -1), nw[0], nw[1], ws[0], 2)
         return self._down_residual(a, ws[1], woq, s).view(residual.shape)

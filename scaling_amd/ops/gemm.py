@@ -32,7 +32,7 @@ from typing import Callable, Iterator, Optional
 import torch
 
 from ._ext import ext, use_native
-from .quant import has_copy, wq_of
+from .quant import has_copy, released_name, wq_of
 
 
 _WGRAD_RAGGED = os.environ.get("SCALING_AMD_WGRAD_RAGGED", "1") != "0"
@@ -142,6 +142,37 @@ def mm_nt(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.matmul(a, b.t())
 
 
+def check_no_graph(name: str, *tensors: Optional[torch.Tensor]) -> None:
+    """Raises where a call through the released weight ``name`` would build an autograd graph: its values exist only as
+    a quantised copy, which has no backward."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{name}: its bf16 weights were released (quantize_weights(release_dense=True)); a forward "
+                           "that builds an autograd graph is not possible -- run it under torch.no_grad()")
+
+
+def _linear_released(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor],
+                     wq: Optional[tuple[str, torch.Tensor, torch.Tensor]]) -> torch.Tensor:
+    """``linear`` for a released weight (``ops/quant.py``): every row count computes from the quantised copy -- the
+    decode kernels within ``decode_rows_limit()`` as for a kept weight, the prefill GEMM (``csrc/kernels/qgemm.hip``)
+    for everything else --, and ``w`` is never read.  No copy or no kernel for the call: ``RuntimeError``."""
+    name = released_name(w)
+    check_no_graph(name, x, w, b)
+    if wq is None:
+        wq = wq_of(w)
+    if wq is None:
+        raise RuntimeError(f"{name}: its bf16 weights were released and it has no valid quantised copy")
+    K = x.shape[-1]
+    rows = x.numel() // K if K else 0
+    if rows > 0 and use_native(x) and w.dim() == 2 and K == w.shape[1] and (b is None or b.dtype == x.dtype):
+        x2 = x.reshape(rows, K)
+        if rows <= decode_rows_limit() and decode_kernel(rows, wq[0] + "_ok")(x2, wq[1], wq[2]):
+            return decode_kernel(rows, wq[0])(x2, wq[1], wq[2], b).reshape(*x.shape[:-1], w.shape[0])
+        if getattr(ext(), "qgemm" + wq[0] + "_ok")(x2, wq[1], wq[2]):
+            return getattr(ext(), "qgemm" + wq[0])(x2, wq[1], wq[2], b, x.new_empty(*x.shape[:-1], w.shape[0]))
+    raise RuntimeError(f"{name}: its bf16 weights were released and no quantised kernel takes this call (x "
+                       f"{tuple(x.shape)} {x.dtype} on {x.device}, weight {tuple(w.shape)})")
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
            wq: Optional[tuple[str, torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """``F.linear(x, w, b)``; decode-sized inputs (<= 4 rows) on the GEMV kernel, inside ``skinny_gemm()``
@@ -154,7 +185,10 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
     A weight quantised by ``ops.quant`` (``wq``: its valid copy with the suffix of the bindings that take it,
     ``("_w8", q, scale)`` or ``("_w4", codes, scales)``, looked up on ``w`` when not given) streams the copy through
     that format's kernels (``csrc/kernels/gemv.hip``, ``skinny.hip``, ``wide.hip``) on that
-    same branch; ``w`` holds the dequantised values, so every other branch computes the same function."""
+    same branch; ``w`` holds the dequantised values, so every other branch computes the same function.  A released
+    weight (``quantize_weights(release_dense=True)``) holds no values: ``_linear_released`` serves it."""
+    if released_name(w) is not None:
+        return _linear_released(x, w, b, wq)
     K = x.shape[-1]
     rows = x.numel() // K if K else 0
     needs_graph = torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or (b is not None and b.requires_grad))

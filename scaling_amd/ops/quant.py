@@ -185,6 +185,52 @@ def has_copy(param: torch.Tensor) -> bool:
     return getattr(param, _ATTR, None) is not None or getattr(param, _ATTR4, None) is not None
 
 
+_REL = "_sa_released"
+
+
+def released_name(param: torch.Tensor) -> Optional[str]:
+    """The name a released parameter was released under, None for every other tensor (a cheap attribute test).
+
+    A released parameter's bf16 storage is gone: it is a zero-stride view of one element that keeps the shape, dtype
+    and device, and the quantised copy beside it (``_sa_w8`` / ``_sa_w4``) is the only encoding of its values.  Its
+    elements must never be read."""
+    return getattr(param, _REL, None)
+
+
+@torch.no_grad()
+def release_parameters(weights: Sequence[torch.Tensor], names: Sequence[str]) -> int:
+    """Frees the bf16 storage of a group quantised by ``quantize_parameters`` (all members together: they share the
+    re-homed group buffer) and marks the members released.  Returns the bytes released."""
+    if any(wq_of(w) is None for w in weights):
+        raise RuntimeError(f"release_parameters: {', '.join(names)}: no valid quantised copy to release to")
+    stub = weights[0].new_zeros(1)
+    freed = 0
+    for w, n in zip(weights, names):
+        freed += w.numel() * w.element_size()
+        w.data = stub.expand(w.shape)
+        if hasattr(w, "_sa_wt_cache"):
+            delattr(w, "_sa_wt_cache")
+        for attr in (_ATTR, _ATTR4):  # the stand-in has its own version counter: stamp the copy again
+            c = getattr(w, attr, None)
+            if c is not None:
+                setattr(w, attr, (c[0], c[1], w._version))
+        setattr(w, _REL, n)
+    return freed
+
+
+def released_group(weights: Sequence[torch.Tensor]) -> torch.Tensor:
+    """The stand-in for the fused ``[sum N, K]`` view of a released group: released itself (zero strides, one element,
+    named after its members), so nothing is materialised and nothing can read it as values."""
+    names = [released_name(w) for w in weights]
+    if any(n is None for n in names):
+        raise RuntimeError(f"a fused group is only partly released: {names}")
+    if len(weights) == 1:
+        return weights[0]
+    g = weights[0].detach().as_strided((sum(w.shape[0] for w in weights), weights[0].shape[1]), (0, 0))
+    setattr(g, _REL, "+".join(names))  # type: ignore[arg-type]
+    return g
+
+
 def wq_of(param: torch.Tensor) -> Optional[tuple[str, torch.Tensor, torch.Tensor]]:
     """``(suffix, copy, scales)`` of the valid quantised copy of ``param`` -- ``("_w8", q, scale)`` or
     ``("_w4", codes, scales)``; the suffix names the bindings that take the copy -- or None."""

@@ -47,9 +47,13 @@ class TransformerInferenceModule(InferenceModule):
                         pipe_partition_method: PipePartitionMethod = PipePartitionMethod.UNIFORM,
                         pipe_partition_overwrite: Optional[list[int]] = None, config_file: Optional[Path] = None,
                         vocab_file: Optional[Path] = None,
-                        weight_quantization: Optional[str] = None) -> "TransformerInferenceModule":
+                        weight_quantization: Optional[str] = None, release_dense: bool = False
+                        ) -> "TransformerInferenceModule":
         """Weights, ``config.yml`` and ``vocab.json`` are expected in the checkpoint directory by default.
-        ``weight_quantization`` (``"fp8_e4m3"`` or ``"mxfp4"``): ``quantize_weights`` is called after loading."""
+        ``weight_quantization`` (``"fp8_e4m3"`` or ``"mxfp4"``): ``quantize_weights`` is called after loading, with
+        ``release_dense`` passed on (it needs ``weight_quantization``)."""
+        if release_dense and weight_quantization is None:
+            raise ValueError("from_checkpoint: release_dense=True needs weight_quantization")
         checkpoint_dir = Path(checkpoint_dir)
         config_file = config_file or checkpoint_dir / "config.yml"
         vocab_file = vocab_file or checkpoint_dir / "vocab.json"
@@ -61,8 +65,31 @@ class TransformerInferenceModule(InferenceModule):
                     tokenizer=Tokenizer.from_file(str(vocab_file)))
         model.load_checkpoint(checkpoint_dir)
         if weight_quantization is not None:
-            model.quantize_weights(weight_quantization)
+            model.quantize_weights(weight_quantization, release_dense=release_dense)
         return model
+
+    def _refuse_if_released(self, what: str) -> None:
+        if getattr(self, "_sa_dense_released", False):
+            raise RuntimeError(f"{what}: the bf16 weights of this module were released "
+                               "(quantize_weights(release_dense=True), a one-way step): their values exist only as "
+                               "quantised copies, which this operation cannot use -- build the module again")
+
+    def state_dict(self, *args: Any, **kwargs: Any) -> Any:
+        self._refuse_if_released("state_dict")
+        return super().state_dict(*args, **kwargs)
+
+    def save_checkpoint(self, *args: Any, **kwargs: Any) -> None:
+        self._refuse_if_released("save_checkpoint")
+        super().save_checkpoint(*args, **kwargs)
+
+    def load_checkpoint(self, *args: Any, **kwargs: Any) -> None:
+        self._refuse_if_released("load_checkpoint")
+        super().load_checkpoint(*args, **kwargs)
+
+    def train(self, mode: bool = True) -> "TransformerInferenceModule":
+        if mode:
+            self._refuse_if_released("train")
+        return super().train(mode)
 
     def _quantization_groups(self, include_lm_head: bool) -> tuple[list[tuple[list[str], list[torch.Tensor]]], dict[str, str]]:
         """``([(names, weights sharing one input), ...], {name: reason it is never quantised})`` of this model."""
@@ -102,7 +129,8 @@ class TransformerInferenceModule(InferenceModule):
                     add(li, "", [("linear", layer.linear)])
         return groups, skipped
 
-    def quantize_weights(self, scheme: str = "fp8_e4m3", include_lm_head: bool = False) -> dict:
+    def quantize_weights(self, scheme: str = "fp8_e4m3", include_lm_head: bool = False,
+                         release_dense: bool = False) -> dict:
         """Opt-in FP8 weight-only decoding (``ops/quant.py``, ``csrc/kernels/gemv.hip``).
 
         Every transformer layer's linear weights (q/k/v or fused qkv, attention dense, the MLP projections), and the
@@ -127,13 +155,30 @@ class TransformerInferenceModule(InferenceModule):
         (the CPU path computes from the parameters).  Returns a summary: ``scheme``, ``tensors``, ``bf16_bytes``,
         ``quantized_bytes`` (the copies incl. scales, whatever the scheme; ``fp8_bytes`` is the same figure for
         ``fp8_e4m3`` and 0 otherwise), ``skipped`` (``{name: reason}``; a weight whose K is not a multiple of 16 --
-        of 32 for ``mxfp4`` -- is skipped)."""
+        of 32 for ``mxfp4`` -- is skipped), ``released_bytes`` (0 unless ``release_dense``).
+
+        ``release_dense=True`` (opt-in, GPU modules only: ``ValueError`` on a CPU module, whose path computes from the
+        parameters): after quantisation every quantised group's bf16 storage is freed, so the weights take 0.5x
+        (``fp8_e4m3``) or about 0.27x (``mxfp4``) of their bf16 memory instead of 1.5x / 1.27x.  A released parameter
+        keeps its shape, dtype and device but holds no values; decode-sized linear layers stream the copy as before and
+        every larger one (the prompt prefill, prefill chunks, eager batches above the row limit) runs the
+        quantised-weight GEMM (``csrc/kernels/qgemm.hip``), which computes the same function from the copy.  Skipped
+        weights (see ``skipped``) stay dense and work as before.  It composes with ``use_cuda_graph``,
+        ``generate_batch``, ``skinny_gemm``, ``wide_batch``, both KV cache options, ``page_size=``,
+        ``generate_continuous`` and ``prefill_chunk=``.  It is a one-way step for the life of the module: a second
+        ``quantize_weights``, a LoRA merge, ``state_dict`` / checkpoint saving or loading, ``train()`` and any forward
+        that would build an autograd graph raise ``RuntimeError`` afterwards (nothing ever reads a released weight as
+        values)."""
         from ...core.nn.linear.main_grad import adjacent_weights
         from ...ops import quant
 
+        self._refuse_if_released("quantize_weights")
         if scheme not in quant.SCHEMES:
             raise ValueError(f"quantize_weights: unknown scheme {scheme!r} (supported: "
                              f"{', '.join(repr(s) for s in quant.SCHEMES)})")
+        if release_dense and any(p.device.type != "cuda" for p in self.parameters()):
+            raise ValueError("quantize_weights: release_dense=True needs the module on a GPU (the CPU path computes "
+                             "from the bf16 parameters)")
         piece = quant.MX_BLOCK if scheme == quant.SCHEME_MXFP4 else quant.PIECE
         if self.devices is None or len(self.devices) != 1:
             raise RuntimeError("quantize_weights: the model must sit on one device")
@@ -148,7 +193,7 @@ class TransformerInferenceModule(InferenceModule):
         for p in self.parameters():  # a parameter carries one copy: those of the other scheme go, head included
             (quant.drop_w8 if scheme == quant.SCHEME_MXFP4 else quant.drop_w4)(p)
         summary = {"scheme": scheme, "tensors": 0, "bf16_bytes": 0, "fp8_bytes": 0, "quantized_bytes": 0,
-                   "skipped": skipped}
+                   "skipped": skipped, "released_bytes": 0}
         for names, weights in groups:
             if any(w.dim() != 2 or w.shape[1] % piece for w in weights):
                 for n, w in zip(names, weights):
@@ -164,6 +209,9 @@ class TransformerInferenceModule(InferenceModule):
             summary["quantized_bytes"] += bq
             if scheme == quant.SCHEME:
                 summary["fp8_bytes"] += bq
+            if release_dense:
+                summary["released_bytes"] += quant.release_parameters(weights, names)
+                self._sa_dense_released = True
         invalidate_transposed_weights()
         return summary
 

@@ -65,6 +65,8 @@ def main() -> None:
     p.add_argument("--weights", default="bf16", help="bf16, fp8_e4m3 or mxfp4 (quantize_weights() first), or a comma list "
                    "measured alternately in this process, --rounds times")
     p.add_argument("--lm-head", action="store_true", help="with quantised --weights: quantise the LM head too")
+    p.add_argument("--release-dense", action="store_true", help="with ONE quantised --weights scheme: "
+                   "quantize_weights(release_dense=True) (one way: the bf16 weights are freed; prefills run qgemm)")
     p.add_argument("--batch", type=int, default=0, help="B >= 1: time batched generation of B prompts")
     p.add_argument("--skinny", action="store_true", help="with --batch: skinny_gemm=True (MFMA kernels, graph up to B = 16)")
     p.add_argument("--kv-cache", default="bf16", help="with --batch: bf16, fp8_e4m3 (generate_batch(kv_cache=...)), or a "
@@ -85,6 +87,8 @@ def main() -> None:
     a.weight_list = a.weights.split(",")
     if any(w not in ("bf16", "fp8_e4m3", "mxfp4") for w in a.weight_list):
         raise SystemExit("--weights: bf16, fp8_e4m3, mxfp4 or a comma list of them")
+    if a.release_dense and (len(a.weight_list) != 1 or a.weight_list[0] == "bf16" or a.rounds != 1):
+        raise SystemExit("--release-dense: one quantised --weights scheme, one round (releasing is a one-way step)")
     if a.kv_list != [None] and a.batch < 1:
         raise SystemExit("--kv-cache needs --batch (the single-sequence eager loop keeps a growing bf16 cache)")
     from scaling_amd.models import llama_architecture
@@ -113,7 +117,7 @@ def main() -> None:
                 quant.drop_w8(prm)
                 quant.drop_w4(prm)
             return None
-        return m.quantize_weights(scheme, include_lm_head=a.lm_head)
+        return m.quantize_weights(scheme, include_lm_head=a.lm_head, release_dense=a.release_dense)
 
     sample_fn, graph_ok, mode = sample_argmax, True, "greedy"
     if a.sampler:
@@ -158,12 +162,15 @@ def single_bench(m, a, arch, prompt, sample_fn, graph_ok, mode, metric, timed, q
     """Batch 1: the eager loop and the captured loop in the model's current weight format."""
     from scaling_amd.transformer.inference.graph_decode import GraphDecoder
 
+    torch.cuda.synchronize()
+    loaded = torch.cuda.memory_allocated()  # after loading (and quantising / releasing), before any cache exists
     m.generate(4, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn)  # warm-up (library handles, tables)
     t1, _ = timed(lambda: m.generate(1, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn))
     tn, eager = timed(lambda: m.generate(a.tokens + 1, input_tokens=prompt, stop_tokens=[], sample_fn=sample_fn))
     eager_ms = 1000.0 * (tn - t1) / a.tokens
     weights = sum(p.numel() * p.element_size() for p in m.parameters())
-    extra = {"weights": a.weights}
+    extra = {"weights": a.weights, "release_dense": a.release_dense, "prefill_ms": round(1e3 * t1, 2),
+             "allocated_after_loading_gib": round(loaded / 2**30, 3)}
     if quantised is not None:  # a decode step streams the quantised copies in place of their bf16 parameters
         weights = weights - quantised["bf16_bytes"] + quantised["quantized_bytes"]
         extra.update(lm_head=a.lm_head, quantised_tensors=quantised["tensors"], skipped=len(quantised["skipped"]),
