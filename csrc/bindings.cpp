@@ -291,6 +291,59 @@ c10::optional<at::Tensor> rope_kv_append_paged(const at::Tensor& qkv, const at::
         return c10::nullopt;
     return q;
 }
+// chunked prefill: rope_kv_append_paged for a packed pass.  qkv [T, nq + 2 nkv, hd]; cu_q int32 [nseg + 1], start int64
+// [nseg], block_table int32 [nseg, max_pages], all on the GPU: token t of segment s sits at position start[s] + t -
+// cu_q[s] and its k/v go to pool row block_table[s, p / page] * page + p % page; returns q [T, nq, hd].  Each token is
+// bitwise what rope_kv_append_paged writes for one token at that position (errors included).  cu_q[nseg] must be T: rows
+// of q past the last segment are not written.  All tensors on qkv's device.
+c10::optional<at::Tensor> rope_kv_write_chunk(const at::Tensor& qkv, const at::Tensor& cosb, const at::Tensor& sinb,
+                                              const at::Tensor& cu_q, const at::Tensor& start, int64_t nq, int64_t nkv,
+                                              int64_t rot_dim, bool interleaved, at::Tensor kc, at::Tensor vc,
+                                              at::Tensor err, const at::Tensor& block_table, int64_t page,
+                                              const c10::optional<at::Tensor>& k_scale,
+                                              const c10::optional<at::Tensor>& v_scale) {
+    TORCH_CHECK(err_word(err), "rope_kv_write_chunk: err must be an int32 GPU tensor");
+    check_cuda(qkv, "qkv");
+    TORCH_CHECK(qkv.dim() == 3, "rope_kv_write_chunk: qkv must be [T, nq + 2 nkv, hd]");
+    TORCH_CHECK(page > 0 && page % 32 == 0, "rope_kv_write_chunk: the page size must be a positive multiple of 32");
+    const int64_t T = qkv.size(0), hd = qkv.size(-1), nseg = start.numel();
+    TORCH_CHECK(kc.dim() == 3 && kc.size(0) > 0 && kc.size(0) % page == 0 && kc.size(0) < (int64_t)1 << 31 &&
+                    vc.sizes() == kc.sizes(),
+                "rope_kv_write_chunk: caches must hold a whole number of pages");
+    TORCH_CHECK(cu_q.is_cuda() && cu_q.scalar_type() == at::kInt && cu_q.is_contiguous() && cu_q.numel() == nseg + 1 &&
+                    start.is_cuda() && start.scalar_type() == at::kLong && start.is_contiguous() && nseg >= 1 &&
+                    nseg < (1 << 30),
+                "rope_kv_write_chunk: cu_q must be int32 [nseg + 1] and start int64 [nseg], contiguous GPU tensors");
+    TORCH_CHECK(block_table.is_cuda() && block_table.scalar_type() == at::kInt && block_table.dim() == 2 &&
+                    block_table.size(0) == nseg && block_table.size(1) >= 1 && block_table.stride(1) == 1,
+                "rope_kv_write_chunk: block_table must be an int32 GPU tensor [nseg, max_pages] with unit last stride");
+    for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{&cu_q, &start, &block_table, &cosb, &sinb, &kc, &vc, &err})
+        TORCH_CHECK(t->device() == qkv.device(), "rope_kv_write_chunk: every tensor must be on qkv's device");
+    const bool q8 = k_scale.has_value() || v_scale.has_value();
+    if (q8 && !kv_scales_ok("rope_kv_write_chunk", qkv, kc, vc, k_scale, v_scale, nkv)) return c10::nullopt;
+    const auto cdt = q8 ? kc.scalar_type() : qkv.scalar_type();
+    if (!(qkv.is_contiguous() && qkv.size(1) == nq + 2 * nkv && nq >= 1 && nkv >= 1 && kc.is_contiguous() &&
+          vc.is_contiguous() && kc.size(1) == nkv && kc.size(2) == hd && kc.scalar_type() == cdt &&
+          vc.scalar_type() == cdt && kc.is_cuda() && vc.is_cuda() && cosb.is_cuda() && sinb.is_cuda() &&
+          cosb.scalar_type() == at::kFloat && sinb.scalar_type() == at::kFloat && cosb.is_contiguous() &&
+          sinb.is_contiguous() && cosb.dim() == 2 && cosb.size(0) >= 1 && cosb.size(-1) == rot_dim / 2 &&
+          sinb.sizes() == cosb.sizes() && rot_dim <= hd && (uintptr_t)qkv.data_ptr() % 16 == 0 &&
+          (uintptr_t)kc.data_ptr() % 16 == 0 && (uintptr_t)vc.data_ptr() % 16 == 0 &&
+          (uintptr_t)cosb.data_ptr() % 16 == 0 && (uintptr_t)sinb.data_ptr() % 16 == 0))
+        return c10::nullopt;
+    const at::DeviceGuard g(qkv.device());
+    auto q = at::empty({T, nq, hd}, qkv.options());
+    if (T == 0) return q;
+    const AppendPages pg{block_table.data_ptr<int>(), block_table.stride(0), (int)page, (int)(kc.size(0) / page)};
+    if (!sa_launch::rope_kv_write_chunk(dt(qkv), interleaved, qkv.data_ptr(), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                                        cu_q.data_ptr<int>(), start.data_ptr<int64_t>(), pg, T, (int)nseg,
+                                        cosb.data_ptr<float>(), sinb.data_ptr<float>(), (int)nq, (int)nkv, (int)hd,
+                                        (int)rot_dim, std::min<int64_t>(block_table.size(1) * page, cosb.size(0)),
+                                        err.data_ptr<int>(), cur_stream(), q8 ? k_scale->data_ptr<float>() : nullptr,
+                                        q8 ? v_scale->data_ptr<float>() : nullptr, q8 ? k_scale->stride(0) : 0))
+        return c10::nullopt;
+    return q;
+}
 
 // ------------------------------------------------------------------ cross entropy
 std::vector<at::Tensor> xent_stats(const at::Tensor& logits, const at::Tensor& target, int64_t v0) {
@@ -1379,6 +1432,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rope_kv_append_paged", &rope_kv_append_paged, "paged batched decode: rope_kv_append_batch into the pages a block table names, one launch",
           py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("nq"), py::arg("nkv"), py::arg("rot_dim"), py::arg("interleaved"),
           py::arg("kc"), py::arg("vc"), py::arg("err"), py::arg("block_table"), py::arg("page"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+    m.def("rope_kv_write_chunk", &rope_kv_write_chunk, "chunked prefill: RoPE + paged K/V write of a packed pass of segments, one launch",
+          py::arg("qkv"), py::arg("cos"), py::arg("sin"), py::arg("cu_q"), py::arg("start"), py::arg("nq"), py::arg("nkv"), py::arg("rot_dim"),
+          py::arg("interleaved"), py::arg("kc"), py::arg("vc"), py::arg("err"), py::arg("block_table"), py::arg("page"),
+          py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
     m.def("xent_stats", &xent_stats, "cross-entropy row statistics");
     m.def("xent_bwd", &xent_bwd, "cross-entropy backward");
     m.def("embed_fwd", &embed_fwd, "vocab-parallel embedding forward");

@@ -44,6 +44,14 @@ bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, voi
                     const float* cosb, const float* sinb, int nq, int nkv, int hd, int rd, int64_t lim, int* err,
                     hipStream_t st, int B = 1, int64_t cap = 0, float* k_scale = nullptr, float* v_scale = nullptr,
                     int64_t s_head = 0, const AppendPages* pages = nullptr);
+// chunked prefill: rope_kv_append's paged form for a packed pass of nseg segments, one launch.  x [T][nq + 2 nkv][hd];
+// tokens [cu_q[s], cu_q[s + 1]) are segment s, token t at position start[s] + t - cu_q[s]; pages.table [nseg][stride]
+// (cu_q, start and the table are device memory).  Token t is bitwise what the paged one-token form writes at that
+// position, FP8 pool included; error tokens as there (bit 0 of *err, q zeroed, nothing written).  false = unsupported
+bool rope_kv_write_chunk(int dtype, bool interleaved, const void* x, void* q_out, void* kc, void* vc, const int* cu_q,
+                         const int64_t* start, const AppendPages& pages, int64_t T, int nseg, const float* cosb,
+                         const float* sinb, int nq, int nkv, int hd, int rd, int64_t lim, int* err, hipStream_t st,
+                         float* k_scale = nullptr, float* v_scale = nullptr, int64_t s_head = 0);
 }  // namespace sa_launch
 
 namespace sa_launch {

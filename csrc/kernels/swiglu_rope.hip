@@ -394,6 +394,221 @@ __global__ __launch_bounds__(256) void rope_kv_append_q8_kernel(const u16* __res
 #endif
 }
 
+// max over each aligned group of lg = 1, 2, 4, ... 64 consecutive lanes, every lane of the group gets it.  Up to 16 lanes
+// the exchange is DPP inside a row of 16 (no LDS traffic): xor 1 and xor 2 as quad permutes; once the quads agree,
+// row_half_mirror (lane i <-> 7 - i) brings the other quad's value and row_mirror (i <-> 15 - i) the other half's.
+// max is idempotent, so the mirrored partner serves as well as the xor partner.  All lanes of the group must be active.
+__device__ __forceinline__ float group_max(float v, int lg) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SA_DPP_MAX(CTRL) \
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true)))
+    if (lg >= 2) SA_DPP_MAX(0xB1);   // quad_perm [1, 0, 3, 2]
+    if (lg >= 4) SA_DPP_MAX(0x4E);   // quad_perm [2, 3, 0, 1]
+    if (lg >= 8) SA_DPP_MAX(0x141);  // row_half_mirror
+    if (lg >= 16) SA_DPP_MAX(0x140); // row_mirror
+#undef SA_DPP_MAX
+    if (lg >= 32) v = fmaxf(v, __shfl_xor(v, 16, 64));
+    if (lg >= 64) v = fmaxf(v, __shfl_xor(v, 32, 64));
+#endif
+    return v;
+}
+
+// The rotated fp32 values stay fp32 values until V8::st rounds them, as in the one-token kernels: left alone, hipcc
+// folds an fp16 store's conversion into the rotation's FMA here (v_fma_mixlo_f16: one rounding of the exact result
+// instead of fp32, then fp16), and one element in a few thousand ends an fp16 ulp away from rope_kv_append_kernel's.
+__device__ __forceinline__ void keep_f32(float (&v)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(v[j]));
+}
+
+// Chunked prefill: RoPE + paged K/V write of a whole packed pass in ONE launch (the one-token kernels above take one
+// token per sequence).  x [T][nq + 2 nkv][hd] is the pass's projection, heads q | k | v; the pass is nseg segments,
+// tokens [cu_q[s], cu_q[s + 1]) belong to segment s and token t sits at position p = start[s] + t - cu_q[s]; q heads
+// are rotated into q_out [T][nq][hd], k heads rotated and v heads copied (FP8 pool, Q8: quantised as
+// rope_kv_append_q8_kernel does) into pool row table[s][p / page] * page + p % page.  cu_q, start and the table are
+// read from device memory, so a launch depends on no host value but T and nseg.  Every value goes through append_chunk,
+// V8 and -- Q8 -- kv_finite_bf / e4m3_pack8 exactly as in the one-token kernels: token t is bitwise what
+// rope_kv_append_paged writes for one token at p.
+//
+// Split of work: token-major.  A group of lg = 2^lgs >= hd / 8 consecutive lanes owns one token (lane c of the group
+// holds 16-byte piece c of a row, as in the one-token kernels), a workgroup of 256 lanes a run of tb = 256 / lg
+// consecutive tokens of ONE segment, and blockIdx.y a slice of hpb consecutive heads (the launcher cuts the heads only
+// as far as the grid needs to fill the machine).  blockIdx.x counts (segment, run) tiles; the tile's segment is found by
+// a walk over cu_q with wave-uniform values -- scalar loads, once per wave, no LDS.  The grid holds T / tb + nseg
+// tiles, an upper bound of sum ceil(n_s / tb); surplus workgroups leave.  Position, table entry and pool row are
+// computed once per token and slice.
+// cos / sin: lanes are split once, outside the head loops, into rotating (c < rc) and pass-through lanes, so inside a
+// loop a lane's cos / sin loads are unconditional and loop-invariant (cosb / sinb are __restrict__) and are hoisted:
+// one load of the lane's piece per token and slice, reused by every q and k head of the slice.  The FP8 k / v loop
+// cannot be split that way -- the whole group takes part in the amax exchange -- so there append_chunk reloads the
+// piece per k head (an L1 hit).
+// FP8 form: the lg lanes of a group hold one (token, k or v head) row (lanes >= CR resp. hd / 8 hold zeros), so a wave
+// quantises 64 / lg rows at once (4 at hd = 128); the amax is group_max (DPP), lane 0 of the group writes the scale.
+// Writes: 16 bytes per lane (8 bytes of codes); a group writes one whole hd row, and the tb tokens of a workgroup go to
+// consecutive pool rows except where a page ends.  No LDS, no scratch (profiles/rope_chunk_resources.md).
+// Errors: a token whose position is outside [0, lim) or whose table entry is outside [0, num_pages) -- never
+// dereferenced: the table is read only at p / page < table width -- writes nothing to the pool, zeroes its q rows and
+// sets bit 0 of *err; bit 1: a non-finite k / v value was replaced (Q8).  Tokens outside [0, T) are skipped.
+struct ChunkSegs {
+    const int* cu_q;
+    const int64_t* start;
+    const int* table;
+    int64_t stride;
+    int nseg, page, num_pages;
+    int64_t T;
+};
+
+template <typename T, bool IL, bool Q8>
+__global__ __launch_bounds__(256) void rope_kv_write_chunk_kernel(const T* __restrict__ x, T* __restrict__ q_out,
+                                                                  void* __restrict__ kc_, void* __restrict__ vc_,
+                                                                  float* __restrict__ k_scale, float* __restrict__ v_scale,
+                                                                  int64_t s_head, const float* __restrict__ cosb,
+                                                                  const float* __restrict__ sinb, int nq, int nkv, int hd,
+                                                                  int rd, int64_t lim, int lgs, int hpb,
+                                                                  int* __restrict__ err, ChunkSegs sg) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int half = rd / 2;
+    const int rc = IL ? rd / 8 : half / 8;
+    const int CR = rc + (hd - rd) / 8;
+    const int nh = nq + 2 * nkv;
+    const int lg = 1 << lgs, tb = 256 >> lgs;
+    // the tile's segment (wave-uniform)
+    int64_t tile = blockIdx.x, q0 = 0, q1 = 0;
+    int s = 0;
+    for (; s < sg.nseg; ++s) {
+        q0 = sg.cu_q[s];
+        q1 = sg.cu_q[s + 1];
+        const int64_t nt = q1 > q0 ? (q1 - q0 + tb - 1) >> (8 - lgs) : 0;  // tb = 2^(8 - lgs)
+        if (tile < nt) break;
+        tile -= nt;
+    }
+    if (s == sg.nseg) return;
+    const int c = threadIdx.x & (lg - 1);
+    const int64_t t = q0 + tile * tb + (threadIdx.x >> lgs);
+    const bool live = t >= 0 && t < q1 && t < sg.T;
+    bool ok = false;
+    int64_t p = 0, row = 0;
+    if (live) {
+        p = sg.start[s] + (t - q0);
+        ok = p >= 0 && p < lim;
+        if (ok) {
+            const int pi = (int)p;  // lim < 2^31
+            const int e = sg.table[s * sg.stride + pi / sg.page];
+            ok = (unsigned)e < (unsigned)sg.num_pages;
+            row = (int64_t)e * sg.page + pi % sg.page;
+        }
+    }
+    if (!ok) p = 0;
+    if (live && !ok && c == 0 && blockIdx.y == 0) atomicOr(err, 1);
+    const float* cb = cosb + p * half;
+    const float* sb = sinb + p * half;
+    const int h0 = blockIdx.y * hpb, h1 = min(h0 + hpb, nh);
+    const T* xt = x + t * nh * hd;
+    T* qt = q_out + t * nq * hd;
+    const int hq = min(h1, nq);  // q heads of the slice: [h0, hq)
+    if (!ok) {
+        if (live && 8 * c < hd) {
+            const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            for (int h = h0; h < hq; ++h) V8<T>::st(qt + (int64_t)h * hd + 8 * c, z);
+        }
+        if (!Q8) return;
+    }
+    if (!Q8) {
+        T* kr = (T*)kc_ + row * nkv * hd;
+        T* vr = (T*)vc_ + row * nkv * hd;
+        const int hk = min(h1, nq + nkv);  // q and k heads: [h0, hk)
+        auto out_row = [&](int h) -> T* { return h < nq ? qt + (int64_t)h * hd : kr + (int64_t)(h - nq) * hd; };
+        if (c < rc) {  // rotating lanes: cos / sin are loop-invariant
+            for (int h = h0; h < hk; ++h) {
+                float o0[8], o1[8];
+                int e0, e1;
+                append_chunk<T, IL>(xt + (int64_t)h * hd, c, rc, half, rd, cb, sb, o0, o1, e0, e1);
+                T* orow = out_row(h);
+                keep_f32(o0);
+                V8<T>::st(orow + e0, o0);
+                if (e1 >= 0) {
+                    keep_f32(o1);
+                    V8<T>::st(orow + e1, o1);
+                }
+            }
+        } else if (c < CR) {  // pass-through lanes
+            for (int h = h0; h < hk; ++h) {
+                float o0[8], o1[8];
+                int e0, e1;
+                append_chunk<T, IL>(xt + (int64_t)h * hd, c, rc, half, rd, cb, sb, o0, o1, e0, e1);
+                V8<T>::st(out_row(h) + e0, o0);
+            }
+        }
+        if (8 * c < hd) {
+            for (int h = max(h0, nq + nkv); h < h1; ++h) {  // v: lane c copies piece c
+                float v[8];
+                V8<T>::ld(xt + (int64_t)h * hd + 8 * c, v);
+                V8<T>::st(vr + (int64_t)(h - nq - nkv) * hd + 8 * c, v);
+            }
+        }
+        return;
+    }
+    if constexpr (Q8) {
+        if (ok) {
+            if (c < rc) {
+                for (int h = h0; h < hq; ++h) {
+                    float o0[8], o1[8];
+                    int e0, e1;
+                    append_chunk<T, IL>(xt + (int64_t)h * hd, c, rc, half, rd, cb, sb, o0, o1, e0, e1);
+                    V8<T>::st(qt + (int64_t)h * hd + e0, o0);
+                    if (e1 >= 0) V8<T>::st(qt + (int64_t)h * hd + e1, o1);
+                }
+            } else if (c < CR) {
+                for (int h = h0; h < hq; ++h) {
+                    float o0[8], o1[8];
+                    int e0, e1;
+                    append_chunk<T, IL>(xt + (int64_t)h * hd, c, rc, half, rd, cb, sb, o0, o1, e0, e1);
+                    V8<T>::st(qt + (int64_t)h * hd + e0, o0);
+                }
+            }
+        }
+        // k and v heads: every lane of the workgroup walks the loop (the group's amax exchange needs the whole group)
+        bool bad = false;
+        for (int h = max(h0, nq); h < h1; ++h) {
+            const bool isv = h >= nq + nkv;
+            const int hk = h - nq - (isv ? nkv : 0);
+            const T* xr = xt + (int64_t)h * hd;
+            float o0[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, o1[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            int e0 = -1, e1 = -1;
+            if (ok) {
+                if (isv) {
+                    if (8 * c < hd) {
+                        e0 = 8 * c;
+                        V8<T>::ld(xr + e0, o0);
+                    }
+                } else if (c < CR) {
+                    append_chunk<T, IL>(xr, c, rc, half, rd, cb, sb, o0, o1, e0, e1);
+                }
+            }
+            float am = 0.f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                o0[j] = kv_finite_bf(o0[j], bad);
+                o1[j] = kv_finite_bf(o1[j], bad);
+                am = fmaxf(am, fmaxf(fabsf(o0[j]), fabsf(o1[j])));
+            }
+            am = group_max(am, lg);
+            const uint32_t bits = __float_as_uint(am);
+            const int E = (int)(bits >> 23);
+            int es = (bits & 0x7fffffu) <= 0x600000u ? E - 135 : E - 134;
+            if (es < -100) es = -100;  // covers the subnormal amax (E == 0)
+            const float sc = bits == 0u ? 1.f : __uint_as_float((uint32_t)(es + 127) << 23);
+            const float inv = bits == 0u ? 1.f : __uint_as_float((uint32_t)(127 - es) << 23);
+            uint8_t* orow = (uint8_t*)(isv ? vc_ : kc_) + (row * nkv + hk) * hd;
+            if (e0 >= 0) *reinterpret_cast<uint2*>(orow + e0) = e4m3_pack8(o0, inv);
+            if (e1 >= 0) *reinterpret_cast<uint2*>(orow + e1) = e4m3_pack8(o1, inv);
+            if (ok && c == 0) (isv ? v_scale : k_scale)[(int64_t)hk * s_head + row] = sc;
+        }
+        if (bad) atomicOr(err, 2);
+    }
+#endif
+}
+
 static int grid_for(int64_t n) {
     int64_t g = (n + 255) / 256;
     return (int)(g < 8192 ? (g < 1 ? 1 : g) : 8192);
@@ -440,6 +655,35 @@ bool rope_kv_append(int dtype, bool interleaved, const void* x, void* q_out, voi
     }
 #undef SA_RKVP
 #undef SA_RKV
+    return true;
+}
+bool rope_kv_write_chunk(int dtype, bool interleaved, const void* x, void* q_out, void* kc, void* vc, const int* cu_q,
+                         const int64_t* start, const AppendPages& pages, int64_t T, int nseg, const float* cosb,
+                         const float* sinb, int nq, int nkv, int hd, int rd, int64_t lim, int* err, hipStream_t st,
+                         float* k_scale, float* v_scale, int64_t s_head) {
+    if (pages.table == nullptr || pages.page < 1 || pages.num_pages < 1 || nseg < 1 || T < 1) return false;
+    if (dtype == DT_F32 || hd % 8 || hd > 512 || (interleaved ? rd % 8 : rd % 16) || rd > hd || lim >= ((int64_t)1 << 31))
+        return false;
+    const bool q8 = k_scale != nullptr;
+    if (q8 && (dtype != DT_BF16 || v_scale == nullptr)) return false;
+    int lgs = 0;
+    while ((8 << lgs) < hd) ++lgs;  // lg = 2^lgs lanes per token, the smallest power of two with 8 lg >= hd
+    const int tb = 256 >> lgs, nh = nq + 2 * nkv;
+    const int64_t tiles = T / tb + nseg;  // >= sum ceil(n_s / tb)
+    // head slices: as few as give the machine ~8 waves per SIMD (2048 workgroups of 4 waves on 256 CUs)
+    const int64_t want = (2048 + tiles - 1) / tiles;
+    const int slices = (int)(want < 1 ? 1 : (want > nh ? nh : want));
+    const int hpb = (nh + slices - 1) / slices;
+    if (tiles > 0x7fffffff) return false;
+    const dim3 g((unsigned)tiles, (unsigned)((nh + hpb - 1) / hpb));
+    const ChunkSegs sg{cu_q, start, pages.table, pages.stride, nseg, pages.page, pages.num_pages, T};
+#define SA_RKC(TT, IL, Q8)                                                                                           \
+    hipLaunchKernelGGL((rope_kv_write_chunk_kernel<TT, IL, Q8>), g, 256, 0, st, (const TT*)x, (TT*)q_out, kc, vc,    \
+                       k_scale, v_scale, s_head, cosb, sinb, nq, nkv, hd, rd, lim, lgs, hpb, err, sg)
+    if (q8) { if (interleaved) SA_RKC(u16, true, true); else SA_RKC(u16, false, true); }
+    else if (dtype == DT_BF16) { if (interleaved) SA_RKC(u16, true, false); else SA_RKC(u16, false, false); }
+    else { if (interleaved) SA_RKC(f16, true, false); else SA_RKC(f16, false, false); }
+#undef SA_RKC
     return true;
 }
 void swiglu_fwd(int dtype, const void* a, const void* b, int64_t lda, void* out, int64_t rows, int F, hipStream_t st) {

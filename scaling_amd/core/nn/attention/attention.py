@@ -494,17 +494,53 @@ class PageAllocator:
 
 
 class ChunkPass:
-    """One chunk of a chunked prefill, set on the shared ``PagedDecodeState`` while the chunk is forwarded: the
-    sequence owns ``pages``, the chunk's ``n`` tokens sit at positions ``start .. start + n - 1``.  Every attention
-    layer writes the chunk's K/V rows into the pages (``write_rows``) and attends with ``ops.attention.chunk_attention``
-    over the pool through ``table`` [1, max_pages] (the sequence's row of the block table) and ``k_range`` =
-    [[0, start + n]]."""
+    """One pass of a chunked prefill, set on the shared ``PagedDecodeState`` while it is forwarded: ``nseg >= 1``
+    segments packed into one token axis, segment i = ``segs[i]`` = (pages its sequence owns, start, n): its ``n`` tokens
+    sit at positions ``start .. start + n - 1``.  Every attention layer rotates the pass and writes its K/V rows into
+    the pages (one ``rope_kv_write_chunk`` launch; ``write_rows`` per segment on the unfused path) and attends with
+    ``ops.attention.chunk_attention`` over the pool.
 
-    def __init__(self, pages: Sequence[int], start: int, n: int, table: torch.Tensor) -> None:
-        self.pages, self.start, self.n, self.table = list(pages), start, n, table
-        device = table.device
-        self.k_range = torch.tensor([[0, start + n]], dtype=torch.int32, device=device)
-        self.cu_q = torch.tensor([0, n], dtype=torch.int32, device=device)
+    Device tensors: ``cu_q`` int32 [nseg + 1], ``k_range`` int32 [nseg, 2] = (0, start + n), ``start`` int64 [nseg],
+    ``table`` int32 [nseg, max_pages] (the segments' pages, -1 beyond), ``pos`` int64 [T] the tokens' positions and --
+    with ``ids``, the pass's T token ids -- ``ids`` int64 [T].  All are views of one buffer filled from one host staging buffer (pinned for a GPU) by one asynchronous copy.  Host values
+    for the attention plan: ``T`` tokens, ``max_q`` = max n, ``max_k`` = max (start + n)."""
+
+    def __init__(self, segs: Sequence[tuple[Sequence[int], int, int]], max_pages: int, device: torch.device,
+                 ids: Optional[Sequence[int]] = None) -> None:
+        self.segs = [(list(pages), int(start), int(n)) for pages, start, n in segs]
+        nseg = len(self.segs)
+        assert nseg >= 1 and all(n >= 1 and len(pages) <= max_pages for pages, _, n in self.segs)
+        self.T = sum(n for _, _, n in self.segs)
+        self.max_q = max(n for _, _, n in self.segs)
+        self.max_k = max(start + n for _, start, n in self.segs)
+        T = self.T
+        assert ids is None or len(ids) == T
+        nw = nseg + (T if ids is None else 2 * T)
+        # int64 words first (start, pos, ids), then the int32 fields
+        stage = torch.empty(2 * nw + (nseg + 1) + 2 * nseg + nseg * max_pages, dtype=torch.int32,
+                            pin_memory=device.type == "cuda")
+        wide = stage[: 2 * nw].view(torch.int64)
+        narrow = stage[2 * nw:]
+        if ids is not None:
+            wide[nseg + T :] = torch.tensor(list(ids), dtype=torch.int64)
+        cu, kr, tab = narrow[: nseg + 1], narrow[nseg + 1 : 3 * nseg + 1].view(nseg, 2), narrow[3 * nseg + 1 :].view(nseg, max_pages)
+        tab.fill_(-1)
+        cu[0] = 0
+        t = 0
+        for i, (pages, start, n) in enumerate(self.segs):
+            wide[i] = start
+            wide[nseg + t : nseg + t + n] = torch.arange(start, start + n)
+            t += n
+            cu[i + 1] = t
+            kr[i, 0], kr[i, 1] = 0, start + n
+            tab[i, : len(pages)] = torch.tensor(pages, dtype=torch.int32)
+        dev = stage.to(device, non_blocking=True)
+        wide = dev[: 2 * nw].view(torch.int64)
+        narrow = dev[2 * nw:]
+        self.start, self.pos = wide[:nseg], wide[nseg : nseg + T]
+        self.ids = wide[nseg + T :] if ids is not None else None
+        self.cu_q, self.k_range = narrow[: nseg + 1], narrow[nseg + 1 : 3 * nseg + 1].view(nseg, 2)
+        self.table = narrow[3 * nseg + 1 :].view(nseg, max_pages)
 
 
 class PagedDecodeState(BatchDecodeState):
@@ -956,15 +992,38 @@ class ParallelSelfAttention(torch.nn.Module):
         kv = self.cache.get(cache_index)
         return kv.state.chunk if isinstance(kv, PagedKVCache) else None
 
+    def _chunk_rope_write(self, kv: PagedKVCache, chunk: ChunkPass, base: torch.Tensor, q: torch.Tensor,
+                          k: torch.Tensor, v: torch.Tensor) -> Optional[torch.Tensor]:
+        """RoPE of the pass's q and k and the write of its k / v into the pages as ONE launch
+        (``ext().rope_kv_write_chunk``); returns the rotated q.  Applies on the GPU when q / k / v are the [q | k | v]
+        column blocks of one contiguous projection; None otherwise (the caller runs the unfused ops)."""
+        re = self.rotary_embedding
+        if not (re is not None and use_native(base) and not self.key_query_norm):
+            return None
+        hd, nq, nkv = self.hidden_size_per_attention_head, q.shape[1], k.shape[1]
+        nh, es = nq + 2 * nkv, base.element_size()
+        if not (base.is_contiguous() and base.numel() == chunk.T * nh * hd and q.data_ptr() == base.data_ptr()
+                and k.data_ptr() == base.data_ptr() + nq * hd * es and v.data_ptr() == base.data_ptr() + (nq + nkv) * hd * es
+                and all(t.stride(1) == hd and t.stride(0) == nh * hd for t in (q, k, v))):
+            return None
+        sc = _fp8_scales(kv) or (None, None)
+        return ext().rope_kv_write_chunk(base.view(chunk.T, nh, hd), re.cos_table, re.sin_table, chunk.cu_q, chunk.start,
+                                         nq, nkv, re.dimensions, re.interleaved, kv.k, kv.v, kv.state.err, chunk.table,
+                                         kv.state.page, sc[0], sc[1])
+
     def _chunk_attention(self, kv: PagedKVCache, chunk: ChunkPass, q: torch.Tensor, k: torch.Tensor,
-                         v: torch.Tensor) -> torch.Tensor:
-        """Chunk mode: the chunk's rotated k and v go into the sequence's pages, then its queries attend over the pool
-        (their own rows included) through the chunk's table."""
-        assert self.use_flash_attention and self.causal and q.shape[0] == chunk.n, "chunked prefill: flash, causal"
-        kv.write_rows(chunk.pages, chunk.start, k, v)
+                         v: torch.Tensor, written: bool) -> torch.Tensor:
+        """Chunk mode: every segment's rotated k and v go into its sequence's pages (``written``: the fused kernel has
+        done that), then its queries attend over the pool (their own rows included) through the pass's table."""
+        assert self.use_flash_attention and self.causal and q.shape[0] == chunk.T, "chunked prefill: flash, causal"
+        if not written:
+            t = 0
+            for pages, start, n in chunk.segs:
+                kv.write_rows(pages, start, k[t : t + n], v[t : t + n])
+                t += n
         nl = self.num_local_attention_heads
         return attn_ops.chunk_attention(
-            q, kv.k, kv.v, chunk.cu_q, chunk.k_range, chunk.n, chunk.start + chunk.n, self.scaling_factor, causal=True,
+            q, kv.k, kv.v, chunk.cu_q, chunk.k_range, chunk.max_q, chunk.max_k, self.scaling_factor, causal=True,
             window=self.local_attention_window_size if nl > 0 else None,
             local_heads=self.num_local_attention_heads_per_partition if nl > 0 else None,
             kv_scales=_fp8_scales(kv), block_table=chunk.table, page_size=kv.state.page)
@@ -1183,9 +1242,9 @@ class ParallelSelfAttention(torch.nn.Module):
         batch_kv = self.cache.get(cache_index) if use_cache and not reset_cache else None
         if not isinstance(batch_kv, BatchStaticKVCache):
             batch_kv = None
-        # chunked prefill into a paged cache: x is [1, n, h], one sequence's chunk (no fused decode path applies)
+        # chunked prefill into a paged cache: x is [1, T, h], the pass's segments packed (no fused decode path applies)
         chunk = batch_kv.state.chunk if isinstance(batch_kv, PagedKVCache) else None
-        assert chunk is None or (b == 1 and projected_step is None), "a prefill chunk is one sequence's tokens"
+        assert chunk is None or (b == 1 and projected_step is None), "a prefill pass is one packed row of tokens"
         # FP8 static cache (decode steps only): k / v below are its codes, read with these scales
         kv_scales = _fp8_scales(self.cache.get(cache_index)) if use_cache and not reset_cache else None
         probe("attention.input", x)
@@ -1217,6 +1276,9 @@ class ParallelSelfAttention(torch.nn.Module):
             if (use_cache and not reset_cache and (T == 1 or batch_kv is not None) and not self.key_query_norm
                     and _DECODE_FUSED and chunk is None):
                 fused_append = self._decode_rope_append(base, q, k, v, position_ids, cache_index)
+            chunk_q = self._chunk_rope_write(batch_kv, chunk, base, q, k, v) if chunk is not None else None
+            if chunk_q is not None:  # chunked prefill: RoPE + paged K/V write of the whole pass in one launch
+                return self._output(self._chunk_attention(batch_kv, chunk, chunk_q, k, v, True).reshape(b, s, -1))
             if fused_append is not None:  # graph decode: RoPE + K/V cache append in one launch
                 q, k, v, cumulative_seq_lengths_key = fused_append
             elif self.rotary_embedding is not None:
@@ -1225,7 +1287,7 @@ class ParallelSelfAttention(torch.nn.Module):
                 k = self.rotary_embedding.apply_tokens(k, pos, s)
 
         if chunk is not None:
-            return self._output(self._chunk_attention(batch_kv, chunk, q, k, v).reshape(b, s, -1))
+            return self._output(self._chunk_attention(batch_kv, chunk, q, k, v, False).reshape(b, s, -1))
         if use_cache and fused_append is None:
             if not self.causal:
                 raise ValueError("KV caching is only supported for causal attention.")

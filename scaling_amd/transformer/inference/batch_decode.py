@@ -41,7 +41,7 @@ request has finished is released and refilled with the next request while the ot
 """
 from __future__ import annotations
 
-from typing import Any, Callable, Optional, Sequence
+from typing import Any, Callable, Optional, Sequence, Union
 
 import torch
 
@@ -254,16 +254,21 @@ class ContinuousBatchDecoder:
 
     ``prefill_chunk=C`` (opt-in, a positive multiple of 32; bf16 / fp16 models on one device, flash attention, no
     ``key_query_norm``): ``admit`` forwards the prompt in chunks of at most ``C`` tokens straight into its freshly
-    allocated pages -- every layer writes the chunk's K/V rows (``PagedKVCache.write_rows``) and attends over the pool
-    with ``ops.attention.chunk_attention`` (``csrc/kernels/flash_chunk.hip``) --, so no contiguous copy of the prompt's
+    allocated pages -- every layer rotates the chunk and writes its K/V rows with one launch
+    (``ext().rope_kv_write_chunk``; ``PagedKVCache.write_rows`` on the CPU) and attends over the pool with
+    ``ops.attention.chunk_attention`` (``csrc/kernels/flash_chunk.hip``) --, so no contiguous copy of the prompt's
     K/V, no spare cache index and no ``load_row``; activations are those of one chunk.  The captured step is not
     touched (``captures`` stays 1).  With ``kv_cache="fp8_e4m3"`` the later chunks read the earlier chunks' keys as e4m3
     codes: the prompt's own prefill then sees quantised K/V, which the unchunked admit (prefill against exact bf16
     K/V, quantised afterwards) does not.  Chunks at or below ``ops.gemm.decode_rows_limit()`` rows may run their
     linear layers on the decode kernels.  ``None`` (default) is the unchunked path, unchanged.
 
+    ``admit_many`` admits several requests together (chunk j of every prompt as one packed pass); ``serve`` uses it
+    whenever more than one row is free and more than one request waits.
+
     Not here: preemption or swapping when the pool is full (``admit`` / ``step`` raise), prefix sharing, batched
-    prefill (a prompt is prefilled alone), prefill chunks interleaved with decode steps inside the captured step."""
+    prefill without ``prefill_chunk`` (a prompt is then prefilled alone), prefill chunks interleaved with decode steps
+    inside the captured step."""
 
     def __init__(self, module: Any, max_batch: int, page_size: int = 64, max_pages: int = 1,
                  num_pages: Optional[int] = None, sample_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
@@ -387,20 +392,13 @@ class ContinuousBatchDecoder:
         pages, the row's device state set and its first token drawn with one ``sample_fn`` call on the prefill logits.
         ``ValueError`` for a request that cannot fit ``max_pages`` pages or the model's sequence length, ``RuntimeError``
         naming the pool size when the pool lacks the prompt's pages -- both before anything is written."""
-        n = len(input_tokens)
-        if n < 1 or max_tokens < 1:
-            raise ValueError("ContinuousBatchDecoder.admit: empty prompt or max_tokens < 1")
-        if n + max_tokens > self.state.capacity:
-            raise ValueError(f"ContinuousBatchDecoder.admit: prompt ({n}) + max_tokens ({max_tokens}) exceeds max_pages * "
-                             f"page_size = {self.max_pages} * {self.page_size} = {self.state.capacity}")
-        if self.sequence_limit is not None and n + max_tokens > self.sequence_limit:
-            raise ValueError(f"ContinuousBatchDecoder.admit: prompt ({n}) + max_tokens ({max_tokens}) exceeds the model's "
-                             f"sequence length {self.sequence_limit}")
-        if self.rows[row] is not None:
-            raise ValueError(f"ContinuousBatchDecoder.admit: row {row} holds a request (release it first)")
-        pages = self.allocator.alloc(-(-(n + 1) // self.page_size))  # RuntimeError before anything is written
         if self.prefill_chunk is not None:
-            return self._admit_chunked(row, list(input_tokens), int(max_tokens), index, pages)
+            req = self.admit_many([row], [input_tokens], [max_tokens])[0]
+            req.index = index
+            return req
+        n = len(input_tokens)
+        self._check_request(row, n, max_tokens)
+        pages = self.allocator.alloc(-(-(n + 1) // self.page_size))  # RuntimeError before anything is written
         settings = InferenceSettings(use_cache=True, reset_cache=True, cache_index=self.spare_index, embedding_layers=[-1])
         with torch.no_grad():
             try:
@@ -423,39 +421,81 @@ class ContinuousBatchDecoder:
         self.rows[row] = req
         return req
 
-    def _admit_chunked(self, row: int, tokens: list[int], max_tokens: int, index: Any, pages: list[int]) -> _Request:
-        """``admit`` with ``prefill_chunk``: the prompt goes through the model in chunks that write their K/V straight
-        into ``pages`` and attend over the pool (``ChunkPass``).  The row stays parked until the last chunk is in, so the
-        captured step's rows are not disturbed; the row's table row is written before the first chunk."""
-        n, C, st = len(tokens), self.prefill_chunk, self.state
+    def _check_request(self, row: int, n: int, max_tokens: int) -> None:
+        """``ValueError`` for a request that row ``row`` cannot take; nothing is changed."""
+        if n < 1 or max_tokens < 1:
+            raise ValueError("ContinuousBatchDecoder.admit: empty prompt or max_tokens < 1")
+        if n + max_tokens > self.state.capacity:
+            raise ValueError(f"ContinuousBatchDecoder.admit: prompt ({n}) + max_tokens ({max_tokens}) exceeds max_pages * "
+                             f"page_size = {self.max_pages} * {self.page_size} = {self.state.capacity}")
+        if self.sequence_limit is not None and n + max_tokens > self.sequence_limit:
+            raise ValueError(f"ContinuousBatchDecoder.admit: prompt ({n}) + max_tokens ({max_tokens}) exceeds the model's "
+                             f"sequence length {self.sequence_limit}")
+        if self.rows[row] is not None:
+            raise ValueError(f"ContinuousBatchDecoder.admit: row {row} holds a request (release it first)")
+
+    def admit_many(self, rows: Sequence[int], prompts: Sequence[Sequence[int]],
+                   max_tokens: Union[int, Sequence[int]]) -> list[_Request]:
+        """Batched admission (requires ``prefill_chunk=C``): rows ``rows[i]`` take the requests (``prompts[i]``,
+        ``max_tokens[i]``; one int serves all).  Every request is checked and all pages are allocated first -- a
+        ``ValueError`` or the ``RuntimeError`` of an exhausted pool leaves everything as it was.  Pass j then forwards
+        chunk j (at most C tokens, from position j * C) of every prompt that still has one, packed as one ``ChunkPass``
+        of that many segments whose K/V go straight into the pages; a finished prompt drops out of the later passes, and
+        its last-token logits are kept from the pass in which it ends.  Activations are those of one pass: at most
+        ``len(rows) * C`` tokens.  After the last pass ``sample_fn`` is called once per request, in the order given --
+        the calls of admitting the requests one by one -- and the rows' device state is set.  Until then the rows stay
+        parked, so the captured step is not disturbed (``captures`` stays 1).  If a pass raises, all pages of the call
+        are freed and the rows re-parked."""
+        if self.prefill_chunk is None:
+            raise ValueError("ContinuousBatchDecoder.admit_many: batched admission needs prefill_chunk")
+        rows, toks = [int(r) for r in rows], [list(p) for p in prompts]
+        limits = [int(max_tokens)] * len(rows) if isinstance(max_tokens, int) else [int(m) for m in max_tokens]
+        if not (len(rows) == len(toks) == len(limits)) or len(set(rows)) != len(rows):
+            raise ValueError("ContinuousBatchDecoder.admit_many: one distinct row, prompt and max_tokens per request")
+        if not rows:
+            return []
+        for row, t, m in zip(rows, toks, limits):
+            self._check_request(row, len(t), m)
+        need = [-(-(len(t) + 1) // self.page_size) for t in toks]
+        taken = self.allocator.alloc(sum(need))  # RuntimeError before anything is written
+        pages = [taken[sum(need[:i]) : sum(need[: i + 1])] for i in range(len(rows))]
+        C, st = self.prefill_chunk, self.state
         dev = st.pos.device
         settings = InferenceSettings(use_cache=True, reset_cache=False, cache_index=0, embedding_layers=[-1])
-        ids = torch.tensor(tokens, dtype=torch.long, device=dev).unsqueeze(0)
+        last: list[Any] = [None] * len(rows)
         with torch.no_grad():
             try:
-                st.set_table(row, pages)  # the row itself stays parked at position 0 until assign() below
-                for start in range(0, n, C):
-                    m = min(C, n - start)
-                    st.chunk = ChunkPass(pages, start, m, st.block_table[row : row + 1])
-                    pos = torch.arange(start, start + m, dtype=torch.long, device=dev).unsqueeze(0)
+                for start in range(0, max(len(t) for t in toks), C):
+                    segs = [(i, min(C, len(t) - start)) for i, t in enumerate(toks) if len(t) > start]
+                    st.chunk = ChunkPass([(pages[i], start, m) for i, m in segs], self.max_pages, dev,
+                                         ids=[tok for i, m in segs for tok in toks[i][start : start + m]])
                     with gemm_ops.skinny_gemm(self.skinny_gemm, wide=self.wide_batch):
-                        out = self.module.forward(TextDatasetBatch(input_token_ids=ids[:, start : start + m],
-                                                                   position_ids=pos, inference_settings=settings))
+                        out = self.module.forward(TextDatasetBatch(input_token_ids=st.chunk.ids.unsqueeze(0),
+                                                                   position_ids=st.chunk.pos.unsqueeze(0),
+                                                                   inference_settings=settings))
+                    end = 0
+                    for i, m in segs:
+                        end += m
+                        if start + m == len(toks[i]):  # the prompt ends in this pass
+                            last[i] = out.activations[:, end - 1 : end, :].clone()
             except BaseException:
-                st.park(row)
-                self.allocator.free(pages)
+                for row in rows:
+                    st.park(row)
+                self.allocator.free(taken)
                 raise
             finally:
                 st.chunk = None
-            last = out.activations[:, -1:, :]
-            first = self.sample_fn(last).reshape(1, 1).to(torch.long)
-            st.assign(row, pages, n)
-            self.tok[row : row + 1].copy_(first)
-        req = _Request(index, n, max_tokens, pages)
-        req.tokens.append(int(first.item()))
-        req.logits.append(last.reshape(1, -1))
-        self.rows[row] = req
-        return req
+            reqs = []
+            for i, row in enumerate(rows):
+                first = self.sample_fn(last[i]).reshape(1, 1).to(torch.long)
+                st.assign(row, pages[i], len(toks[i]))
+                self.tok[row : row + 1].copy_(first)
+                req = _Request(None, len(toks[i]), limits[i], pages[i])
+                req.tokens.append(int(first.item()))
+                req.logits.append(last[i].reshape(1, -1))
+                self.rows[row] = req
+                reqs.append(req)
+        return reqs
 
     def release(self, row: int) -> Optional[_Request]:
         """The row's pages go back to the free list and the row is parked; returns the request it held."""
@@ -515,6 +555,16 @@ class ContinuousBatchDecoder:
             return req.tokens[-1] in stops or len(req.tokens) >= req.max_tokens
 
         while nxt < len(requests) or any(r is not None for r in self.rows):
+            # batched admission: with prefill_chunk, several free rows and several waiting requests go in together
+            while self.prefill_chunk is not None and len(self.free_rows) > 1 and len(requests) - nxt > 1:
+                free = self.free_rows[: len(requests) - nxt]
+                batch = requests[nxt : nxt + len(free)]
+                reqs = self.admit_many(free, [t for t, _ in batch], [m for _, m in batch])
+                for row, req in zip(free, reqs):
+                    req.index = nxt
+                    nxt += 1
+                    if over(req):  # done with the prefill's token
+                        finish(row)
             for row in self.free_rows:
                 while nxt < len(requests) and self.rows[row] is None:
                     toks, mt = requests[nxt]
