@@ -1023,13 +1023,24 @@ std::vector<at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const a
 // chunk attention (flash_chunk.hip): query segments of any length over keys in a KV cache.  k_range int32 [nseg, 2] =
 // (first key row, key count) over a slab buffer, or (0, length) with block_table int32 [nseg, max_pages] + page_size
 // over a pool of pages; k_scale / v_scale: FP8 codes as in fa_fwd.  splits = 0: the plan; > 0 forces that many.
+// key_bias float32 [key rows]: added to the score of every query with the key at that buffer row (dense slab keys only).
 std::vector<at::Tensor> fa_chunk(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& cu_q,
                                  int64_t max_q, double scale, bool causal, int64_t window, int64_t local_heads,
                                  int64_t max_k, const at::Tensor& k_range, const c10::optional<at::Tensor>& k_scale,
                                  const c10::optional<at::Tensor>& v_scale, const c10::optional<at::Tensor>& block_table,
-                                 int64_t page_size, int64_t splits) {
+                                 int64_t page_size, int64_t splits, const c10::optional<at::Tensor>& key_bias) {
     const bool q8 = k_scale.has_value() || v_scale.has_value();
     check_qkv(q, "q");
+    if (key_bias.has_value()) {  // ValueError, not TORCH_CHECK's RuntimeError: the argument itself is refused
+        const auto refuse_unless = [](bool ok, const std::string& why) { if (!ok) throw py::value_error("chunk_attn: " + why); };
+        refuse_unless(!block_table.has_value(), "key_bias with block_table (paged keys) is not supported");
+        refuse_unless(!q8, "key_bias with k_scale / v_scale (FP8 keys) is not supported");
+        refuse_unless(key_bias->is_cuda() && key_bias->device() == q.device() && key_bias->scalar_type() == at::kFloat &&
+                      key_bias->dim() == 1 && key_bias->is_contiguous() && key_bias->size(0) == k.size(0),
+                      "key_bias must be a contiguous float32 tensor on q's device with one value per row of k (" +
+                      std::to_string(k.size(0)) + ")");
+        refuse_unless(scale > 0 && std::isfinite(1.0 / scale), "key_bias needs a positive softmax scale");
+    }
     if (q8) {
         TORCH_CHECK(k_scale.has_value() && v_scale.has_value(), "chunk_attn: k_scale and v_scale come together");
         for (const at::Tensor* t : {&k, &v}) {
@@ -1085,6 +1096,7 @@ std::vector<at::Tensor> fa_chunk(const at::Tensor& q, const at::Tensor& k, const
         d.block_table = block_table->data_ptr<int>(); d.bt_stride = block_table->stride(0); d.page = (int)page_size;
         d.num_pages = (int)(k.size(0) / page_size); d.max_pages = (int)block_table->size(1);
     }
+    if (key_bias.has_value()) { d.key_bias = key_bias->data_ptr<float>(); d.kb_mul = (float)(1.0 / scale); }
     const int grp = d.Hq / d.Hkv;
     const int64_t mk = max_k > 0 ? max_k : (pg ? block_table->size(1) * page_size : k.size(0));
     sa_launch::fa_chunk_plan(max_q, mk, d.Hkv, grp, nseg, pg, (int)splits, d.split_keys, d.nsplit);
@@ -1458,6 +1470,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("src"), py::arg("scratch"), py::arg("bytes"), py::arg("us"), py::arg("nwg") = 16);
     m.def("dropout_add", &dropout_add, "residual + dropout(x) with a hashed keep mask", py::arg("x"), py::arg("res"), py::arg("p"), py::arg("seed"));
     m.def("fa_fwd", &fa_fwd, "flash attention forward (bf16/fp16, optional attention dropout)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("max_k") = -1, py::arg("k_range") = py::none(), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("page_size") = 0);
-    m.def("fa_chunk", &fa_chunk, "chunk attention over a KV cache (slab ranges or pages; bf16/fp16/FP8 keys), forward only", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("local_heads"), py::arg("max_k"), py::arg("k_range"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("page_size") = 0, py::arg("splits") = 0);
+    m.def("fa_chunk", &fa_chunk, "chunk attention over a KV cache (slab ranges or pages; bf16/fp16/FP8 keys), forward only", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("max_q"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("local_heads"), py::arg("max_k"), py::arg("k_range"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(), py::arg("block_table") = py::none(), py::arg("page_size") = 0, py::arg("splits") = 0, py::arg("key_bias") = py::none());
     m.def("fa_bwd", &fa_bwd, "flash attention backward (optional strided dq/dk/dv outputs)", py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("cu_q"), py::arg("cu_k"), py::arg("max_q"), py::arg("max_k"), py::arg("scale"), py::arg("causal"), py::arg("window"), py::arg("dq_out") = py::none(), py::arg("dk_out") = py::none(), py::arg("dv_out") = py::none(), py::arg("p_drop") = 0.0, py::arg("seed") = 0, py::arg("local_heads") = -1, py::arg("rope_cos") = py::none(), py::arg("rope_sin") = py::none(), py::arg("rope_pos") = py::none(), py::arg("rope_dim") = 0, py::arg("rope_seq") = 1, py::arg("rope_interleaved") = false);
 }

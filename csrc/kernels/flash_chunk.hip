@@ -41,6 +41,24 @@
 //
 // Split-K (nsplit > 1): the key span is cut at multiples of 64 keys; a workgroup writes its unnormalised (O, m, l) in
 // fa_decode_kernel's partial layout and fa_decode_combine merges them.  With one split o and lse are written directly.
+//
+// Key bias (KB; dense bf16 / fp16 slab keys only): score = scale * q.k + key_bias[buffer row of the key], one fp32 value
+// per key (attention-score manipulation: log of a suppression factor, -10000 or -inf for factor 0).  In S^T = K Q^T the
+// key is the accumulator's ROW, so a lane needs 32 biases per tile (rows 32b + 8g + 4h + 0..3), each wanted by the 32
+// lanes of its half.  The bias is NOT added by VALU: the QK accumulators are SEEDED with key_bias / scale (= key_bias *
+// kb_mul, multiplied once where the value is loaded) instead of zero, the MFMAs add the raw q.k on top, and the softmax
+// that follows is the unbiased kernel's instruction for instruction -- (bias / scale + q.k) * scale_log2 is the biased
+// score in base 2, rounded at the magnitude fp32 math rounds bias + scale * q.k at.  So the running max sees the bias,
+// lse includes it (the split-K partials and the combine stay valid unchanged), a masked key stays masked (the mask
+// overwrites the accumulator), an all-zero bias gives the unbiased kernel's bits, and -inf needs no care: the seed
+// stays -inf through the MFMAs (K and Q are finite), and an all -inf row of a tile takes the guards an all-masked row
+// takes already (no rescale from m = -inf, exp2(-inf) = 0): no inf - inf, no NaN in m, l or O.
+// Transport: thread t < 64 fetches the bias of key kt + t with the K/V register staging of that tile (one VGPR, in
+// flight across the MFMA phase; keys at or past the span end load nothing and read 0) and writes it beside the tile's
+// K/V image (256 B per buffer) at the staging store, so it rides the existing barrier; a lane then reads its 32 seeds
+// as 8 ds_read_b128 (two addresses per instruction, broadcast: conflict-free) straight into the accumulator registers.
+// Through LDS rather than registers alone because a lane's 32 values for tile t + 1, held across tile t's MFMA phase on
+// top of tile t's, are 64 VGPRs the D = 128 form does not have below its 256-register cap.
 #include <algorithm>
 
 #include "flash_attn.h"
@@ -70,9 +88,10 @@ __device__ __forceinline__ u32x4 dequant8(u32x2 c, float sc) {
     return w;
 }
 
-template <int D, bool F16, bool Q8, bool PG>
+template <int D, bool F16, bool Q8, bool PG, bool KB = false>
 __global__ __launch_bounds__(256, 2) void fa_chunk_kernel(DecArgs a) {
     static_assert(!(F16 && Q8), "FP8 K/V: bf16 queries only");
+    static_assert(!(KB && (Q8 || PG)), "key bias: dense slab keys only");
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int KT = 64, TILE = KT * D * 2, NKS = D / 16, NT = D / 32;
     constexpr int CPR = D / 8, RPP = 256 / CPR, NPT = KT / RPP;  // 8-element chunks per row, rows per pass, passes
@@ -165,7 +184,11 @@ __global__ __launch_bounds__(256, 2) void fa_chunk_kernel(DecArgs a) {
     u16x8 rk[Q8 ? 1 : NPT], rv[Q8 ? 1 : NPT];
     u32x2 ck[Q8 ? NPT : 1], cv[Q8 ? NPT : 1];
     float sk[Q8 ? NPT : 1], sv[Q8 ? NPT : 1];
+    float rb = 0.f;  // KB: accumulator seed of key kt + tid (threads 0..63)
     auto load = [&](int kt) {
+        if constexpr (KB) {  // k0s + kt + tid < k0s + khi <= k_rows = the bias's length
+            if (tid < KT) rb = kt + tid < khi ? a.key_bias[(int64_t)k0s + kt + tid] * a.kb_mul : 0.f;
+        }
         const int b0 = half_base(kt, 0), b1 = half_base(kt, 1);
 #pragma unroll
         for (int i = 0; i < NPT; ++i) {
@@ -184,7 +207,12 @@ __global__ __launch_bounds__(256, 2) void fa_chunk_kernel(DecArgs a) {
             }
         }
     };
+    // KB: the 64 seeds of the tile in buffer `buf` (0 or 1), behind the four K/V images
+    auto seeds = [&](const char* buf) -> char* { return smem + 4 * TILE + (buf == smem ? 0 : 4 * KT); };
     auto store = [&](char* buf) {
+        if constexpr (KB) {
+            if (tid < KT) *reinterpret_cast<float*>(seeds(buf) + 4 * tid) = rb;
+        }
 #pragma unroll
         for (int i = 0; i < NPT; ++i) {
             const int row = r0 + RPP * i;
@@ -219,6 +247,17 @@ __global__ __launch_bounds__(256, 2) void fa_chunk_kernel(DecArgs a) {
         if (pw0 >= P || (a.causal && kt > qhi_w + off)) return;
         const char* V = K + TILE;
         f32x16 s[2] = {f32x16{}, f32x16{}};
+        if constexpr (KB) {  // registers 4g .. 4g + 3 of block b are keys kt + 32b + 8g + 4h + 0..3
+            const char* sd = seeds(K) + 16 * h;
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 w = *reinterpret_cast<const f32x4*>(sd + 128 * b + 32 * g);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) s[b][4 * g + j] = w[j];
+                }
+        }
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
@@ -359,6 +398,22 @@ void launch(const DecArgs& a, int max_q, hipStream_t st) {
     constexpr int smem = 4 * 64 * D * 2;
     const bool pg = a.block_table != nullptr;
     bool q8 = false;
+    if (a.key_bias != nullptr) {  // the caller has refused pages and FP8 scales; 512 B more LDS for the seeds
+        constexpr int smem_kb = smem + 2 * 64 * 4;
+        if constexpr (smem_kb > 65536) {  // more than 64 KiB of dynamic LDS is asked for once per device (sample.hip)
+            static bool asked[64] = {};
+            int dev = 0;
+            (void)hipGetDevice(&dev);
+            if (dev < 0 || dev >= 64 || !asked[dev]) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fa_chunk_kernel<D, F16, false, false, true>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, smem_kb);
+                if (dev >= 0 && dev < 64) asked[dev] = true;
+            }
+        }
+        hipLaunchKernelGGL((fa_chunk_kernel<D, F16, false, false, true>), grid, block, smem_kb, st, a);
+        if (a.nsplit > 1) sa_launch::fa_decode_combine(a, D, F16, st);
+        return;
+    }
     if constexpr (!F16) {
         q8 = a.k_scale != nullptr;
         if (q8 && pg) hipLaunchKernelGGL((fa_chunk_kernel<D, false, true, true>), grid, block, smem, st, a);

@@ -123,6 +123,10 @@ struct DecArgs {
     // pool row block_table[s * bt_stride + j / page] * page + j % page.  max_pages = the table's width; an entry
     // outside [0, num_pages) is never dereferenced (its keys are masked), entries past a segment's length never read
     const int* block_table; int64_t bt_stride; int page, num_pages, max_pages;
+    // fa_chunk only, dense slab keys only (no block_table, no k_scale): key_bias[t] is added to the score of every
+    // query with the key at buffer row t (t as in k_range; -inf allowed).  kb_mul = 1 / softmax scale: the kernel
+    // seeds its raw q.k accumulators with key_bias * kb_mul
+    const float* key_bias; float kb_mul;
 };
 namespace sa_launch {
 void fa_decode_plan(int64_t max_k, int Hkv, int nseg, int& split_keys, int& nsplit);

@@ -1213,6 +1213,22 @@ class ParallelSelfAttention(torch.nn.Module):
             return None
         return qr, kv.k, kv.v, st.k_range
 
+    def _flash_key_bias(self, manip: torch.Tensor, log_additive: Union[bool, list[bool]], x: torch.Tensor,
+                        use_cache: bool, reset_cache: bool) -> Optional[torch.Tensor]:
+        """The score manipulation as the chunk kernel's per-key bias (fp32 ``[b * s]``, token order), or None when the
+        call has to take the dense torch attention: a decode step over a cache, autograd, a multiplicative or mixed
+        batch, a materialised tensor (one that lost the zero query stride ``EmbeddingInput`` gives it, e.g. across a
+        pipeline boundary), or a dtype the kernel does not take."""
+        if (use_cache and not reset_cache) or torch.is_grad_enabled() or (self.training and self.dropout_attention_probs > 0):
+            return None
+        if not (log_additive is True or (isinstance(log_additive, (list, tuple)) and all(log_additive))):
+            return None
+        if manip.dim() != 4 or manip.shape[1] != 1 or not (manip.shape[2] == 1 or manip.stride(2) == 0):
+            return None
+        if use_native(x) and x.dtype not in (torch.bfloat16, torch.float16):
+            return None
+        return manip[:, 0, 0, :].float().reshape(-1)
+
     # ------------------------------------------------------------------ forward
     def forward(
         self,
@@ -1247,6 +1263,21 @@ class ParallelSelfAttention(torch.nn.Module):
         assert chunk is None or (b == 1 and projected_step is None), "a prefill pass is one packed row of tokens"
         # FP8 static cache (decode steps only): k / v below are its codes, read with these scales
         kv_scales = _fp8_scales(self.cache.get(cache_index)) if use_cache and not reset_cache else None
+        # AtMan score manipulation under flash attention: a per-key log-additive bias goes to the chunk kernel
+        # (key_bias); every other manipulated call takes the dense torch attention below -- none is dropped
+        manip = attention_scores_manipulation
+        key_bias: Optional[torch.Tensor] = None
+        dense_manip = False
+        if manip is not None and self.use_flash_attention:
+            key_bias = self._flash_key_bias(manip, attentions_score_manipulation_log_additive,
+                                            x if projected_base is None else projected_base, use_cache, reset_cache)
+            dense_manip = key_bias is None
+            static_kv = isinstance(self.cache.get(cache_index), (StaticKVCache, BatchStaticKVCache))
+            if dense_manip and (self.num_local_attention_heads > 0 or projected_step is not None
+                                or (use_cache and not reset_cache and static_kv)):
+                raise ValueError("attention score manipulation: this call needs the dense torch attention (only a "
+                                 "log-additive per-key manipulation of a prompt pass runs on the flash kernel), which "
+                                 "supports neither local attention heads nor the static, batched or paged KV caches")
         probe("attention.input", x)
         if projected_step is not None:  # graph decode: norm + q/k/v GEMV + RoPE + K/V append were one launch
             q, k, v, cumulative_seq_lengths_key = projected_step
@@ -1262,7 +1293,7 @@ class ParallelSelfAttention(torch.nn.Module):
             if lora_in_base:  # fresh views of the updated GEMM output
                 q, k, v = self._views(base, T)
             probe("attention.qkv", base)
-            if not use_cache and not reset_cache and cumulative_seq_lengths_key is None:
+            if not use_cache and not reset_cache and cumulative_seq_lengths_key is None and manip is None:
                 fused = self._fused_rope_attention(base, q, k, v, position_ids, s, cumulative_seq_lengths, max_seq_length,
                                                    lora_in_base=lora_in_base)
                 if fused is not None:
@@ -1311,7 +1342,16 @@ class ParallelSelfAttention(torch.nn.Module):
             self.cache[cache_index] = (None, None)
 
         Tk = k.shape[0]
-        if self.use_flash_attention:
+        if key_bias is not None:  # a prompt pass (Tk == T): the chunk kernel over the pass's own rotated keys
+            cu = cumulative_seq_lengths.to(torch.int32)
+            max_q = max_seq_length if max_seq_length is not None else s
+            nl = self.num_local_attention_heads
+            hidden = attn_ops.chunk_attention(
+                q, k, v, cu, torch.stack([cu[:-1], cu[1:] - cu[:-1]], dim=1), max_q, max_q, self.scaling_factor,
+                causal=self.causal, window=self.local_attention_window_size if nl > 0 else None,
+                local_heads=self.num_local_attention_heads_per_partition if nl > 0 else None,
+                key_bias=key_bias).reshape(b, s, -1)
+        elif self.use_flash_attention and not dense_manip:
             cu_k = cumulative_seq_lengths_key if cumulative_seq_lengths_key is not None else cumulative_seq_lengths
             # segments never cross a batch row, so the row length bounds every segment: no host sync
             max_q = max_seq_length if max_seq_length is not None else s

@@ -14,7 +14,8 @@ class MaskedSoftmaxConfig(BaseConfig):
     kernel: MaskedSoftmaxKernel = Field(
         MaskedSoftmaxKernel.TORCH,
         description="'flash_attention' selects the MI355X HIP flash-attention kernel; 'torch' the unfused "
-        "masked-softmax path (needed for attention score manipulation)",
+        "masked-softmax path (a flash layer takes it per call for a score manipulation that is not a log-additive "
+        "per-key bias of a prompt pass)",
     )
     softmax_in_fp32: bool = Field(False, description="Cast scores to fp32 before the softmax")
     scale: float = Field(1.0, description="Scale with which scores are multiplied (not divided!) before softmax")

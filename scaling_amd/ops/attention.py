@@ -73,8 +73,9 @@ def dropout_seed(device: torch.device) -> int:
 
 def attention_reference(q, k, v, cu_q, cu_k, scale, causal, window=-1, dropout_p: float = 0.0, training=False,
                         dropout_seed_value: Optional[int] = None, local_heads: Optional[int] = None,
-                        key_ranges: Optional[torch.Tensor] = None):
+                        key_ranges: Optional[torch.Tensor] = None, key_bias: Optional[torch.Tensor] = None):
     """Dense per-segment fp32 attention (numerical oracle and CPU path). q:[T,Hq,D], k/v:[Tk,Hk,D].
+    ``key_bias`` [Tk]: added to the scores of the key at that row of k, before the masks.
     With ``dropout_seed_value`` the dropout mask is the fused kernel's (:func:`dropout_keep_mask`).
     ``local_heads``: only q heads [0, local_heads) use ``window``, the others attend globally.
     ``key_ranges`` [nseg, 2] = (first key row, key count): segment i reads keys [start, start + count) instead of
@@ -97,6 +98,8 @@ def attention_reference(q, k, v, cu_q, cu_k, scale, causal, window=-1, dropout_p
         ki = k[ks:ke].float().repeat_interleave(rep, dim=1).transpose(0, 1)
         vi = v[ks:ke].float().repeat_interleave(rep, dim=1).transpose(0, 1)
         s = torch.matmul(qi, ki.transpose(1, 2)) * scale
+        if key_bias is not None:
+            s = s + key_bias[ks:ke].float()
         Lq, Lk = qe - qs, ke - ks
         qpos = torch.arange(Lq, device=q.device)[:, None] + (Lk - Lq)
         kpos = torch.arange(Lk, device=q.device)[None, :]
@@ -435,7 +438,7 @@ def chunk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlen
                     local_heads: Optional[int] = None,
                     kv_scales: Optional[tuple[torch.Tensor, torch.Tensor]] = None,
                     block_table: Optional[torch.Tensor] = None, page_size: Optional[int] = None,
-                    splits: int = 0, return_lse: bool = False) -> Any:
+                    splits: int = 0, return_lse: bool = False, key_bias: Optional[torch.Tensor] = None) -> Any:
     """Attention of query chunks of ANY length over keys held in a KV cache (``csrc/kernels/flash_chunk.hip``): what a
     chunked prefill, prefix reuse or a multi-token verification step needs and :func:`flash_attention` refuses above
     ``32 / group`` queries.  Forward only (raises under grad).
@@ -448,7 +451,10 @@ def chunk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlen
     ``ctx + n``.  ``kv_scales`` = (k_scale, v_scale) float32 ``[Hk, rows]``: k / v are e4m3 codes (bfloat16 queries
     only); the result equals the bf16 call on the dequantised K/V bit for bit, as the paged call equals the slab call
     on the gathered rows.  ``max_seqlen_q`` / ``max_seqlen_k`` size the grid and the split plan (host values, no
-    read-back); ``splits`` > 0 forces a split count.  On CPU tensors the dense reference runs on the gathered,
+    read-back); ``splits`` > 0 forces a split count.  ``key_bias`` float32 ``[rows]`` (slab keys in bfloat16 / float16
+    only): ``key_bias[r]`` is added to the scaled score of every query with the key at buffer row ``r``, before the
+    masks and the softmax (a per-key log-additive score manipulation; ``-inf`` removes a key); ``lse`` includes it, and
+    all zeros give the bits of the call without it.  On CPU tensors the dense reference runs on the gathered,
     dequantised keys.  GPU tensors require the extension."""
     from .quant import dequantize_kv_rows
 
@@ -457,6 +463,11 @@ def chunk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlen
     if key_ranges is None:
         raise ValueError("chunk attention: key_ranges ((start, length) per segment) are required")
     paged = block_table is not None or page_size is not None
+    if key_bias is not None:
+        if paged:
+            raise ValueError("chunk attention: key_bias with block_table (paged keys) is not supported")
+        if kv_scales is not None:
+            raise ValueError("chunk attention: key_bias with kv_scales (FP8 keys) is not supported")
     if paged:
         page_size = _check_pages(q, k, cu_seqlens_q, key_ranges, block_table, page_size)
     if kv_scales is not None:
@@ -480,14 +491,14 @@ def chunk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlen
         if ks is not None:
             k, v = dequantize_kv_rows(k, ks, q.dtype), dequantize_kv_rows(v, vs, q.dtype)
         out = attention_reference(q, k, v, cu_seqlens_q, None, scale, causal, win, local_heads=local_heads,
-                                  key_ranges=key_ranges)
+                                  key_ranges=key_ranges, key_bias=key_bias)
         return (out, None) if return_lse else out
     if q.dtype not in (torch.bfloat16, torch.float16) or (kv_scales is not None and q.dtype != torch.bfloat16):
         raise ValueError(f"chunk attention supports bfloat16 / float16 queries (bfloat16 with kv_scales), got {q.dtype}")
     ks, vs = kv_scales if kv_scales is not None else (None, None)
     o, lse = ext().fa_chunk(q, k, v, cu_seqlens_q.to(torch.int32), int(max_seqlen_q), float(scale), bool(causal), win,
                             -1 if local_heads is None else int(local_heads), int(max_seqlen_k), key_ranges, ks, vs,
-                            block_table, int(page_size) if paged else 0, int(splits))
+                            block_table, int(page_size) if paged else 0, int(splits), key_bias)
     return (o, lse) if return_lse else o
 
 

@@ -104,7 +104,10 @@ class BaseEmbeddingInput(BaseLayer[TextDatasetBatchGeneric, TransformerLayerIO, 
         params = st.inference_control_parameters
         b, s = act.shape[0], act.shape[1]
         assert len(params) == b, "number of inference_control_parameters does not match batch size"
-        manip = torch.zeros(b, 1, s, s, device=act.device, dtype=act.dtype)
+        # one value per (batch row, key position): built compact and returned as a [b, 1, s, s] view whose query
+        # dimension has stride 0 -- the same values for the dense attention, and the mark by which the flash path
+        # knows the manipulation is a per-key bias (ParallelSelfAttention._flash_key_bias)
+        manip = torch.zeros(b, 1, 1, s, device=act.device, dtype=act.dtype)
         for i, p in enumerate(params):
             if not p.control_log_additive:
                 manip[i] = 1.0
@@ -142,7 +145,7 @@ class BaseEmbeddingInput(BaseLayer[TextDatasetBatchGeneric, TransformerLayerIO, 
                     manip[i, :, :, j] = -10000.0 if f == 0.0 else float(torch.log(torch.tensor(f)))
                 else:
                     manip[i, :, :, j] = f
-        return manip
+        return manip.expand(b, 1, s, s)
 
     def get_control_factor_from_cosine_similarity(self, control_factor: float, cosine_similarity: float) -> float:
         if 0 <= cosine_similarity <= 1.0:
