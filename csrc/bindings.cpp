@@ -1339,12 +1339,73 @@ std::vector<at::Tensor> sample_logits(const at::Tensor& logits, const at::Tensor
     if (want_info) return {tokens, info};
     return {tokens};
 }
+
+// Row-table form: tokens [B] int64 for logits [B, V]; every table column is a 1-D tensor of at least B entries on the
+// logits' device (any stride), hist [>= B, H] int32 with unit stride along H.  A [r : r + 1] slice of every column is a
+// valid table for a [1, V] call.  info (optional) [B, 2] int32 is written for active rows only.  Raises ValueError.
+at::Tensor sample_rows(const at::Tensor& logits, const at::Tensor& active, const at::Tensor& temperature,
+                       const at::Tensor& top_k, const at::Tensor& top_p, const at::Tensor& seed, const at::Tensor& step,
+                       const at::Tensor& rep, const at::Tensor& inv_rep, const at::Tensor& presence,
+                       const at::Tensor& hist_len, const at::Tensor& hist, const c10::optional<at::Tensor>& info) {
+    TORCH_CHECK_VALUE(logits.is_cuda() && logits.dim() == 2, "sample_rows: logits must be a [B, V] GPU tensor");
+    const int64_t B = logits.size(0), V = logits.size(1);
+    TORCH_CHECK_VALUE(V >= 1 && V <= sa_launch::sample_rows_max_vocab(), "sample_rows: vocabulary size must be in [1, ",
+                      sa_launch::sample_rows_max_vocab(), "]");
+    TORCH_CHECK_VALUE(B <= INT32_MAX, "sample_rows: too many rows");
+    TORCH_CHECK_VALUE(logits.stride(1) == 1 || V == 1, "sample_rows: logits need a unit last stride");
+    TORCH_CHECK_VALUE(B <= 1 || logits.stride(0) >= 0, "sample_rows: negative row stride");
+    auto column = [&](const at::Tensor& t, at::ScalarType type, const char* name) {
+        TORCH_CHECK_VALUE(t.scalar_type() == type, "sample_rows: column ", name, " must be ", type);
+        TORCH_CHECK_VALUE(t.device() == logits.device(), "sample_rows: column ", name, " must be on the logits' device");
+        TORCH_CHECK_VALUE(t.dim() == 1 && t.size(0) >= B, "sample_rows: column ", name, " needs at least ", B, " entries");
+        return t.size(0) > 1 ? t.stride(0) : 0;
+    };
+    SampleRowTable t{};
+    t.s_active = column(active, at::kInt, "active");
+    t.s_temperature = column(temperature, at::kFloat, "temperature");
+    t.s_top_k = column(top_k, at::kInt, "top_k");
+    t.s_top_p = column(top_p, at::kFloat, "top_p");
+    t.s_seed = column(seed, at::kInt, "seed");
+    t.s_step = column(step, at::kLong, "step");
+    t.s_rep = column(rep, at::kFloat, "rep");
+    t.s_inv_rep = column(inv_rep, at::kFloat, "inv_rep");
+    t.s_presence = column(presence, at::kFloat, "presence");
+    t.s_hist_len = column(hist_len, at::kInt, "hist_len");
+    TORCH_CHECK_VALUE(hist.scalar_type() == at::kInt && hist.device() == logits.device() && hist.dim() == 2 &&
+                      hist.size(0) >= B, "sample_rows: hist must be int32 [>= B, H] on the logits' device");
+    TORCH_CHECK_VALUE(hist.size(1) <= INT32_MAX && (hist.size(1) <= 1 || hist.stride(1) == 1),
+                      "sample_rows: hist needs a unit stride along H");
+    if (info.has_value())
+        TORCH_CHECK_VALUE(info->scalar_type() == at::kInt && info->device() == logits.device() && info->dim() == 2 &&
+                          info->size(0) == B && info->size(1) == 2 && info->is_contiguous(),
+                          "sample_rows: info must be a contiguous int32 [B, 2] on the logits' device");
+    t.active = active.data_ptr<int>(); t.temperature = temperature.data_ptr<float>();
+    t.top_k = top_k.data_ptr<int>(); t.top_p = top_p.data_ptr<float>(); t.seed = seed.data_ptr<int>();
+    t.step = step.data_ptr<int64_t>(); t.rep = rep.data_ptr<float>(); t.inv_rep = inv_rep.data_ptr<float>();
+    t.presence = presence.data_ptr<float>(); t.hist_len = hist_len.data_ptr<int>();
+    t.hist = hist.data_ptr<int>(); t.hist_ld = hist.size(0) > 1 ? hist.stride(0) : 0; t.H = (int)hist.size(1);
+    const int code = dt(logits);
+    const at::DeviceGuard g(logits.device());
+    auto tokens = at::empty({B}, logits.options().dtype(at::kLong));
+    if (B > 0)
+        sa_launch::sample_rows(code, logits.data_ptr(), B > 1 ? logits.stride(0) : 0, B, (int)V,
+                               tokens.data_ptr<int64_t>(), info.has_value() ? info->data_ptr<int>() : nullptr, t,
+                               cur_stream());
+    return tokens;
+}
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("sample_logits", &sample_logits, "one draw per row of logits [B, V] after top-k / top-p / temperature "
           "(graph-safe: the step is read on the device)", py::arg("logits"), py::arg("step"), py::arg("seed"),
           py::arg("temperature"), py::arg("top_k"), py::arg("top_p"), py::arg("want_info") = false);
+    m.def("sample_rows", &sample_rows, "one draw per active row of logits [B, V] with per-row parameters, penalties and "
+          "history from a device-resident table; appends the token and advances the row's counters in the same launch",
+          py::arg("logits"), py::arg("active"), py::arg("temperature"), py::arg("top_k"), py::arg("top_p"),
+          py::arg("seed"), py::arg("step"), py::arg("rep"), py::arg("inv_rep"), py::arg("presence"),
+          py::arg("hist_len"), py::arg("hist"), py::arg("info") = py::none());
+    m.def("sample_rows_max_vocab", []() { return sa_launch::sample_rows_max_vocab(); },
+          "the largest vocabulary of the row-table sampling kernel (its penalty bitmap lives in LDS)");
     m.def("sample_max_resident_vocab", []() { return sa_launch::sample_max_resident(); },
           "the largest vocabulary whose row the sampling kernel stages in LDS");
     m.doc() = "scaling_amd CDNA4 (gfx950) HIP kernels";

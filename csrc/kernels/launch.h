@@ -199,6 +199,22 @@ void sample(int dtype, const void* logits, int64_t ld, int64_t B, int V, int64_t
             const int64_t* step, uint32_t seed, int top_k, float top_p, float temperature, hipStream_t st);
 }  // namespace sa_launch
 
+// sample.hip, row-table form: one entry per row of logits, column X's entry b at X[b * s_X] (element strides).
+// active 0: tokens[b] = 0 and nothing else is written.  temperature 0: greedy.  seed holds 32 bits.  rep / inv_rep /
+// presence: penalties of the tokens in hist[b, :hist_len[b]] (hist [B, H], row stride hist_ld, unit stride along H).
+// The launch appends the token to hist (while hist_len < H) and advances hist_len and step.
+struct SampleRowTable {
+    const int* active; const float* temperature; const int* top_k; const float* top_p; const int* seed;
+    int64_t* step; const float* rep; const float* inv_rep; const float* presence; int* hist_len;
+    int64_t s_active, s_temperature, s_top_k, s_top_p, s_seed, s_step, s_rep, s_inv_rep, s_presence, s_hist_len;
+    int* hist; int64_t hist_ld; int H;
+};
+namespace sa_launch {
+int sample_rows_max_vocab();  // the largest V whose penalty bitmap fits in LDS
+void sample_rows(int dtype, const void* logits, int64_t ld, int64_t B, int V, int64_t* tokens, int* info,
+                 const SampleRowTable& t, hipStream_t st);
+}  // namespace sa_launch
+
 // gemv.hip epi 3: interleaved RoPE of q / k and the K/V cache append at the device-side position
 struct GemvRope {
     const float* cosb; const float* sinb; const int64_t* pos;

@@ -194,6 +194,114 @@ template <typename T> struct Passes { static constexpr int n = 4; };
 template <> struct Passes<u16> { static constexpr int n = 2; };       // bf16: 16 significant bits
 template <> struct Passes<_Float16> { static constexpr int n = 3; };  // fp16 -> fp32: 1 + 8 + 10 bits
 
+// The cuts and the draw over a row whose maximum mx is finite; every thread of the workgroup calls it.  top_k in [0, V],
+// top_p >= 0; uniform24() gives the draw's 24 random bits; info2 (may be null) receives (kept count, bits of the cut).
+// Returns the token on wave 0 (the caller's lane 0 stores it) and -1 on the other waves.
+template <int NP, typename RowT, typename U>
+__device__ __forceinline__ int cut_and_draw(const RowT& row, int V, float mx, int top_k, float top_p, float inv_t,
+                                            U uniform24, int* info2, char* smem) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    // ---- cuts
+    uint32_t cut = f2key(-INFINITY);
+    if (top_k > 0 && top_k < V) {
+        const u64 kt = (u64)(top_k - 1);
+        cut = radix_select<NP>(row, [kt](u64) { return kt; }, [](float, uint32_t) { return (u64)1; }, smem);
+    }
+    if (top_p < 1.0f) {
+        const uint32_t kcut = cut;
+        const double p = (double)top_p;
+        // the first pass's bins also give the total mass Z (the maximum alone contributes 2^40), an integer sum and so
+        // the same whatever the order: cum > p Z  <=>  cum > floor(p Z)
+        cut = radix_select<NP>(
+            row,
+            [p](u64 Z) {
+                const u64 t = (u64)(p * (double)Z);
+                return t < Z ? t : Z - 1;  // p just below 1 after rounding: the cut is the smallest massive value
+            },
+            [mx, kcut](float x, uint32_t key) { return key >= kcut ? (u64)((double)__expf(x - mx) * kFix) : (u64)0; },
+            smem);
+    }
+
+    // ---- draw.  Tokens in rows of 64; the 16 waves split the current range of rows, sum their weights (per-wave
+    // partials added in wave order: reproducible), the range narrows to the wave whose share holds the target, until
+    // one row is left; one wave scan resolves it.  Every pass after the first covers 1/16 of the previous one.
+    const float c = inv_t * 1.44269504088896340736f;
+    auto weight = [&](int i, bool& kept) {
+        kept = false;
+        if (i >= V) return 0.f;
+        const float x = row.at(i);
+        kept = f2key(x) >= cut && x > -INFINITY;
+        return kept ? exp2f((x - mx) * c) : 0.f;
+    };
+    double* seg = reinterpret_cast<double*>(smem + kOffSeg);
+    int* segc = reinterpret_cast<int*>(smem + kOffCnt);
+    int lo = 0, n = (V + 63) >> 6;
+    double target = 0.0;
+    bool first = true;
+    for (;;) {
+        const int rpw = (n + kWaves - 1) / kWaves;
+        const int r0 = lo + wid * rpw, r1 = min(r0 + rpw, lo + n);
+        double acc = 0.0;
+        int cnt = 0;
+#pragma unroll 4
+        for (int rr = r0; rr < r1; ++rr) {
+            bool kept;
+            acc += (double)weight(rr * 64 + lane, kept);
+            cnt += kept;
+        }
+        acc = wave_sum_d(acc);
+        if (first) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+        }
+        __syncthreads();  // the previous level's readers are done
+        if (lane == 0) { seg[wid] = acc; segc[wid] = cnt; }
+        __syncthreads();
+        if (first) {
+            double S = 0.0;
+            int kept_n = 0;
+            for (int w = 0; w < kWaves; ++w) { S += seg[w]; kept_n += segc[w]; }
+            target = (double)uniform24() * (1.0 / 16777216.0) * S;
+            if (tid == 0 && info2) {
+                info2[0] = kept_n;
+                info2[1] = (int)__float_as_uint(key2f(cut));
+            }
+            first = false;
+        }
+        // the wave whose share holds the target: first w with prefix(w) > target, else (the target sat on the upper
+        // edge: summation-order rounding) the last wave with any weight
+        int sel = -1, last = 0;
+        double before = 0.0, pre = 0.0, lastpre = 0.0;
+        for (int w = 0; w < kWaves; ++w) {
+            const double s = seg[w];
+            if (s > 0.0) { last = w; lastpre = pre; }
+            if (sel < 0 && pre + s > target) { sel = w; before = pre; }
+            pre += s;
+        }
+        if (sel < 0) { sel = last; before = lastpre; }
+        target -= before;
+        const int end = lo + n;
+        lo += sel * rpw;
+        n = min(rpw, end - lo);
+        if (rpw == 1) break;
+    }
+    if (wid != 0) return -1;
+
+    bool kept;
+    const double wv = (double)weight(lo * 64 + lane, kept);
+    double inc = wv;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double o = shfl_up_d(inc, d);
+        if (lane >= d) inc += o;
+    }
+    const u64 hm = __ballot(wv > 0.0 && inc > target), pm = __ballot(wv > 0.0);
+    int token = lo * 64;
+    if (hm) token += __ffsll((long long)hm) - 1;
+    else if (pm) token += 63 - __clzll((long long)pm);
+    return min(token, V - 1);
+}
+
 struct SampleArgs {
     const void* logits; int64_t ld; int V;
     int64_t* tokens; int* info;
@@ -204,7 +312,7 @@ struct SampleArgs {
 template <typename T, bool RES>
 __global__ void __launch_bounds__(kThreads) sample_kernel(SampleArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int V = a.V;
     const int64_t r = blockIdx.x;
     const T* g = reinterpret_cast<const T*>(a.logits) + r * a.ld;
@@ -246,110 +354,19 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(SampleArgs a) {
         return;
     }
 
-    // ---- cuts
-    uint32_t cut = f2key(-INFINITY);
-    if (a.top_k > 0 && a.top_k < V) {
-        const u64 kt = (u64)(a.top_k - 1);
-        cut = radix_select<NP>(row, [kt](u64) { return kt; }, [](float, uint32_t) { return (u64)1; }, smem);
-    }
-    if (a.top_p < 1.0f) {
-        const uint32_t kcut = cut;
-        const double p = (double)a.top_p;
-        // the first pass's bins also give the total mass Z (the maximum alone contributes 2^40), an integer sum and so
-        // the same whatever the order: cum > p Z  <=>  cum > floor(p Z)
-        cut = radix_select<NP>(
-            row,
-            [p](u64 Z) {
-                const u64 t = (u64)(p * (double)Z);
-                return t < Z ? t : Z - 1;  // p just below 1 after rounding: the cut is the smallest massive value
-            },
-            [mx, kcut](float x, uint32_t key) { return key >= kcut ? (u64)((double)__expf(x - mx) * kFix) : (u64)0; },
-            smem);
-    }
-
-    // ---- draw.  Tokens in rows of 64; the 16 waves split the current range of rows, sum their weights (per-wave
-    // partials added in wave order: reproducible), the range narrows to the wave whose share holds the target, until
-    // one row is left; one wave scan resolves it.  Every pass after the first covers 1/16 of the previous one.
-    const float c = a.inv_t * 1.44269504088896340736f;
-    auto weight = [&](int i, bool& kept) {
-        kept = false;
-        if (i >= V) return 0.f;
-        const float x = row.at(i);
-        kept = f2key(x) >= cut && x > -INFINITY;
-        return kept ? exp2f((x - mx) * c) : 0.f;
-    };
-    double* seg = reinterpret_cast<double*>(smem + kOffSeg);
-    int* segc = reinterpret_cast<int*>(smem + kOffCnt);
-    int lo = 0, n = (V + 63) >> 6;
-    double target = 0.0;
-    bool first = true;
-    for (;;) {
-        const int rpw = (n + kWaves - 1) / kWaves;
-        const int r0 = lo + wid * rpw, r1 = min(r0 + rpw, lo + n);
-        double acc = 0.0;
-        int cnt = 0;
-#pragma unroll 4
-        for (int rr = r0; rr < r1; ++rr) {
-            bool kept;
-            acc += (double)weight(rr * 64 + lane, kept);
-            cnt += kept;
-        }
-        acc = wave_sum_d(acc);
-        if (first) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-        }
-        __syncthreads();  // the previous level's readers are done
-        if (lane == 0) { seg[wid] = acc; segc[wid] = cnt; }
-        __syncthreads();
-        if (first) {
-            double S = 0.0;
-            int kept_n = 0;
-            for (int w = 0; w < kWaves; ++w) { S += seg[w]; kept_n += segc[w]; }
+    // ---- cuts and draw; u is a hash of (seed, step, row)
+    const int token = cut_and_draw<NP>(
+        row, V, mx, a.top_k, a.top_p, a.inv_t,
+        [&]() {
             const int64_t step = *a.step;
             uint32_t h = mix32(a.seed + 0x9e3779b9u);
             h = mix32(h ^ (uint32_t)step);
             h = mix32(h + (uint32_t)((uint64_t)step >> 32));
             h = mix32(h ^ ((uint32_t)r * 0x85ebca6bu));
-            target = (double)(h >> 8) * (1.0 / 16777216.0) * S;
-            if (tid == 0 && a.info) {
-                a.info[2 * r] = kept_n;
-                a.info[2 * r + 1] = (int)__float_as_uint(key2f(cut));
-            }
-            first = false;
-        }
-        // the wave whose share holds the target: first w with prefix(w) > target, else (the target sat on the upper
-        // edge: summation-order rounding) the last wave with any weight
-        int sel = -1, last = 0;
-        double before = 0.0, pre = 0.0, lastpre = 0.0;
-        for (int w = 0; w < kWaves; ++w) {
-            const double s = seg[w];
-            if (s > 0.0) { last = w; lastpre = pre; }
-            if (sel < 0 && pre + s > target) { sel = w; before = pre; }
-            pre += s;
-        }
-        if (sel < 0) { sel = last; before = lastpre; }
-        target -= before;
-        const int end = lo + n;
-        lo += sel * rpw;
-        n = min(rpw, end - lo);
-        if (rpw == 1) break;
-    }
-    if (wid != 0) return;
-
-    bool kept;
-    const double wv = (double)weight(lo * 64 + lane, kept);
-    double inc = wv;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double o = shfl_up_d(inc, d);
-        if (lane >= d) inc += o;
-    }
-    const u64 hm = __ballot(wv > 0.0 && inc > target), pm = __ballot(wv > 0.0);
-    int token = lo * 64;
-    if (hm) token += __ffsll((long long)hm) - 1;
-    else if (pm) token += 63 - __clzll((long long)pm);
-    if (lane == 0) a.tokens[r] = min(token, V - 1);
+            return h >> 8;
+        },
+        a.info ? a.info + 2 * r : nullptr, smem);
+    if (token >= 0 && lane == 0) a.tokens[r] = token;
 }
 
 template <typename T>
@@ -373,11 +390,239 @@ void launch_t(const SampleArgs& a, int64_t B, hipStream_t st) {
     SA_CHECK_LAUNCH();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Row-table form: every quantity that is one scalar per launch above is read per row from a device-resident table
+// (struct of arrays, one entry per decoder row), so the rows of one launch serve unrelated requests.  Per active row:
+//   1. the row's history sets bits of a V-bit bitmap in LDS (atomicOr: order-independent); ids outside [0, V) are ignored;
+//   2. a seen token's fp32 logit x becomes (x > 0 ? x * inv_rep : x * rep) - presence, two separately rounded operations;
+//      a resident row is adjusted once while it is staged, a streamed row inside PenRow on every pass;
+//   3. the cuts and the draw above, with the row's own top_k / top_p / temperature and u = hash(seed[b], step[b], 0);
+//      temperature 0: the lowest index among the maxima, info = (number of maxima, bits of the maximum);
+//   4. tokens[b] = token; hist[b, hist_len[b]] = token and ++hist_len[b] while hist_len[b] < H; ++step[b].
+// An inactive row writes tokens[b] = 0 and nothing else.
+//
+// LDS: histograms (kOffRow bytes) | bitmap (V bits, rounded up to 16 bytes) | fp32 row image (resident rows).
+// V = 32768: 18.5 KiB + 4 KiB + 128 KiB = 150.5 KiB of the 160 KiB; a streamed row of kMaxRowsV = 2^20 tokens:
+// 18.5 KiB + 128 KiB.
+constexpr int kMaxRowsV = 1 << 20;
+constexpr int kLdsLimit = 160 * 1024;
+__host__ __device__ constexpr int bitmap_bytes(int V) { return ((V + 127) >> 7) << 4; }
+static_assert(kOffRow + bitmap_bytes(kMaxResident) + (kMaxResident + 4) * 4 <= kLdsLimit, "resident carve");
+static_assert(kOffRow + bitmap_bytes(kMaxRowsV) <= kLdsLimit, "streamed carve");
+
+// PEN: the row has penalties.  Without them this is Row (no bitmap is built or read), and the fp32 images of bf16 /
+// fp16 logits keep their constant low key bits; a penalised logit is a full fp32 value and needs all four radix passes.
+template <typename T, bool RES, bool PEN>
+struct PenRow {
+    static constexpr int kPasses = PEN ? 4 : Passes<T>::n;
+    const T* g;
+    const float* img;  // LDS image of the penalised row, token i at img[i]
+    const uint32_t* bm;
+    int V, head;
+    float rep, inv_rep, presence;
+    // the penalised fp32 image of raw logit x at token i
+    __device__ __forceinline__ float fix(int i, float x) const {
+        x = canon(x);
+        if constexpr (PEN) {
+            if ((bm[i >> 5] >> (i & 31)) & 1u)
+                x = canon(__fsub_rn(x > 0.0f ? __fmul_rn(x, inv_rep) : __fmul_rn(x, rep), presence));
+        }
+        return x;
+    }
+    __device__ __forceinline__ float at(int i) const {
+        if constexpr (RES) return img[i];
+        else return fix(i, to_f32(g[i]));
+    }
+    template <typename F>
+    __device__ __forceinline__ void each(F f) const {
+        if constexpr (RES) {
+#pragma unroll 4
+            for (int i = threadIdx.x; i < V; i += kThreads) f(img[i]);
+        } else {
+            global_row<T>(g, V, head,
+                          [&](int i0, const float (&v)[8]) {
+#pragma unroll
+                              for (int j = 0; j < 8; ++j) f(fix(i0 + j, v[j]));
+                          },
+                          [&](int i, float x) { f(fix(i, x)); });
+        }
+    }
+};
+
+template <typename U> struct Col {  // one table column: entry b at p[b * s]
+    U* p; int64_t s;
+    __device__ __forceinline__ U& operator[](int64_t b) const { return p[b * s]; }
+};
+
+struct RowsArgs {
+    const void* logits; int64_t ld; int V;
+    int64_t* tokens; int* info;
+    Col<const int> active, top_k, seed;
+    Col<const float> temperature, top_p, rep, inv_rep, presence;
+    Col<int64_t> step;
+    Col<int> hist_len;
+    int* hist; int64_t hist_ld; int H;
+};
+
+// One active row; PEN is block-uniform.  Returns the token on tid 0 (-1 elsewhere) once info has been written.
+template <typename T, bool RES, bool PEN>
+__device__ __forceinline__ int rows_body(const RowsArgs& a, int64_t r, int hlen, int64_t step, char* smem) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int V = a.V;
+    const float temp = a.temperature[r];
+    const T* g = reinterpret_cast<const T*>(a.logits) + r * a.ld;
+    float* red = reinterpret_cast<float*>(smem + kOffRed);
+    int* segc = reinterpret_cast<int*>(smem + kOffCnt);
+    uint32_t* bm = reinterpret_cast<uint32_t*>(smem + kOffRow);
+    const int head = min(V, (int)(((16 - ((uintptr_t)g & 15)) & 15) / sizeof(T)));
+    float* img = reinterpret_cast<float*>(smem + kOffRow + bitmap_bytes(V)) + ((4 - (head & 3)) & 3);
+    const PenRow<T, RES, PEN> row{g, img, bm, V, head, a.rep[r], a.inv_rep[r], a.presence[r]};
+    int* info2 = a.info ? a.info + 2 * r : nullptr;
+
+    // ---- penalty bitmap
+    if constexpr (PEN) {
+        for (int i = tid; i < (bitmap_bytes(V) >> 2); i += kThreads) bm[i] = 0u;
+        __syncthreads();
+        const int* hist = a.hist + r * a.hist_ld;
+        const int n = min(max(hlen, 0), a.H);
+        for (int i = tid; i < n; i += kThreads) {
+            const int t = hist[i];
+            if ((unsigned)t < (unsigned)V) atomicOr(&bm[t >> 5], 1u << (t & 31));
+        }
+        __syncthreads();
+    }
+
+    // ---- stage the penalised row + its max
+    float mx = -INFINITY;
+    global_row<T>(g, V, head,
+                  [&](int i0, const float (&v)[8]) {
+                      f32x4 lo4, hi4;
+#pragma unroll
+                      for (int j = 0; j < 4; ++j) {
+                          lo4[j] = row.fix(i0 + j, v[j]);
+                          hi4[j] = row.fix(i0 + j + 4, v[j + 4]);
+                          mx = fmaxf(mx, fmaxf(lo4[j], hi4[j]));
+                      }
+                      if constexpr (RES) {
+                          *reinterpret_cast<f32x4*>(img + i0) = lo4;
+                          *reinterpret_cast<f32x4*>(img + i0 + 4) = hi4;
+                      }
+                  },
+                  [&](int i, float x) {
+                      x = row.fix(i, x);
+                      if constexpr (RES) img[i] = x;
+                      mx = fmaxf(mx, x);
+                  });
+    mx = block_max(mx, red);  // its barriers also publish the LDS image
+    if (mx == -INFINITY) {    // nothing can be drawn (block-uniform)
+        if (tid == 0 && info2) { info2[0] = 0; info2[1] = (int)__float_as_uint(-INFINITY); }
+        return tid == 0 ? 0 : -1;
+    }
+
+    // ---- greedy: the lowest index among the maxima (exact, no uniform)
+    if (temp == 0.0f) {
+        int best = V, cnt = 0;
+        for (int i = tid; i < V; i += kThreads)
+            if (row.at(i) == mx) { best = min(best, i); ++cnt; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            best = min(best, __shfl_xor(best, o, 64));
+            cnt += __shfl_xor(cnt, o, 64);
+        }
+        int* wbest = reinterpret_cast<int*>(red);
+        __syncthreads();  // block_max's readers of red are done
+        if (lane == 0) { wbest[wid] = best; segc[wid] = cnt; }
+        __syncthreads();
+        if (tid != 0) return -1;
+        for (int w = 1; w < kWaves; ++w) { best = min(best, wbest[w]); cnt += segc[w]; }
+        if (info2) { info2[0] = cnt; info2[1] = (int)__float_as_uint(mx); }
+        return min(best, V - 1);
+    }
+
+    // ---- cuts and draw over the penalised row.  The row term of sample_kernel's hash chain is the constant 0: a draw
+    // belongs to the request, not to the decoder row it occupies.
+    const int token = cut_and_draw<PenRow<T, RES, PEN>::kPasses>(
+        row, V, mx, max(0, min(a.top_k[r], V)), fmaxf(a.top_p[r], 0.0f), __fdiv_rn(1.0f, temp),
+        [&]() {
+            uint32_t h = mix32((uint32_t)a.seed[r] + 0x9e3779b9u);
+            h = mix32(h ^ (uint32_t)step);
+            h = mix32(h + (uint32_t)((uint64_t)step >> 32));
+            return mix32(h) >> 8;
+        },
+        info2, smem);
+    return tid == 0 ? token : -1;
+}
+
+template <typename T, bool RES>
+__global__ void __launch_bounds__(kThreads) sample_rows_kernel(RowsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int64_t r = blockIdx.x;
+    if (a.active[r] == 0) {
+        if (threadIdx.x == 0) a.tokens[r] = 0;
+        return;
+    }
+    // what the launch advances, read by every thread before tid 0 writes it behind the body's barriers
+    const int64_t step = a.step[r];
+    const int hlen = a.hist_len[r];
+    const bool pen = a.rep[r] != 1.0f || a.presence[r] != 0.0f;
+    const int token = pen ? rows_body<T, RES, true>(a, r, hlen, step, smem)
+                          : rows_body<T, RES, false>(a, r, hlen, step, smem);
+    if (token < 0) return;  // tid 0 goes on: the token and the state advance
+    a.tokens[r] = token;
+    if (hlen >= 0 && hlen < a.H) {
+        a.hist[r * a.hist_ld + hlen] = token;
+        a.hist_len[r] = hlen + 1;
+    }
+    a.step[r] = step + 1;
+}
+
+// more than 64 KiB of dynamic LDS has to be asked for, once per device and kernel
+template <typename K>
+void allow_lds(K kernel, int bytes, bool (&asked)[64]) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !asked[dev]) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  bytes);
+        if (dev >= 0 && dev < 64) asked[dev] = true;
+    }
+}
+
+template <typename T>
+void launch_rows_t(const RowsArgs& a, int64_t B, hipStream_t st) {
+    const size_t base = (size_t)kOffRow + (size_t)bitmap_bytes(a.V);
+    if (a.V <= kMaxResident) {
+        const size_t lds = base + ((size_t)a.V + 4) * 4;
+        static bool asked[64] = {};
+        if (lds > 65536)
+            allow_lds(&sample_rows_kernel<T, true>, kOffRow + bitmap_bytes(kMaxResident) + (kMaxResident + 4) * 4, asked);
+        hipLaunchKernelGGL((sample_rows_kernel<T, true>), dim3((unsigned)B), dim3(kThreads), lds, st, a);
+    } else {
+        static bool asked[64] = {};
+        if (base > 65536) allow_lds(&sample_rows_kernel<T, false>, kOffRow + bitmap_bytes(kMaxRowsV), asked);
+        hipLaunchKernelGGL((sample_rows_kernel<T, false>), dim3((unsigned)B), dim3(kThreads), base, st, a);
+    }
+    SA_CHECK_LAUNCH();
+}
+
 }  // namespace
 }  // namespace sa
 
 namespace sa_launch {
 int sample_max_resident() { return sa::kMaxResident; }
+int sample_rows_max_vocab() { return sa::kMaxRowsV; }
+
+void sample_rows(int dtype, const void* logits, int64_t ld, int64_t B, int V, int64_t* tokens, int* info,
+                 const SampleRowTable& t, hipStream_t st) {
+    sa::RowsArgs a{logits, ld, V, tokens, info,
+                   {t.active, t.s_active}, {t.top_k, t.s_top_k}, {t.seed, t.s_seed},
+                   {t.temperature, t.s_temperature}, {t.top_p, t.s_top_p}, {t.rep, t.s_rep},
+                   {t.inv_rep, t.s_inv_rep}, {t.presence, t.s_presence},
+                   {t.step, t.s_step}, {t.hist_len, t.s_hist_len}, t.hist, t.hist_ld, t.H};
+    if (dtype == DT_F32) sa::launch_rows_t<float>(a, B, st);
+    else if (dtype == DT_BF16) sa::launch_rows_t<sa::u16>(a, B, st);
+    else sa::launch_rows_t<sa::f16>(a, B, st);
+}
 
 void sample(int dtype, const void* logits, int64_t ld, int64_t B, int V, int64_t* tokens, int* info,
             const int64_t* step, uint32_t seed, int top_k, float top_p, float temperature, hipStream_t st) {

@@ -41,6 +41,7 @@ request has finished is released and refilled with the next request while the ot
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Any, Callable, Optional, Sequence, Union
 
 import torch
@@ -51,6 +52,9 @@ from ...core.nn.attention.attention import (BatchDecodeState, BatchStaticKVCache
                                             ParallelSelfAttention, check_kv_cache_scheme, check_page_size)
 from ..data import TextDatasetBatch
 from ..data.inference_settings import InferenceSettings
+from .sample import SamplingParams
+
+SamplingArg = Union[None, SamplingParams, Sequence[SamplingParams]]  # None, one for all, or one per request
 
 
 class BatchDecoder:
@@ -266,6 +270,13 @@ class ContinuousBatchDecoder:
     ``admit_many`` admits several requests together (chunk j of every prompt as one packed pass); ``serve`` uses it
     whenever more than one row is free and more than one request waits.
 
+    Per-request sampling (``sample_fn=sample.RequestSampler(max_batch, history >= max_pages * page_size)``, or
+    ``sampling=True`` / a default ``SamplingParams`` to have one built): ``admit`` / ``admit_many`` / ``serve`` take
+    ``sampling=`` (``SamplingParams``), the row's entry of the sampler's table is filled before the first token is drawn
+    on the one-row slice, ``release`` parks it, and the captured step's single sampling launch serves every row with
+    its own parameters, penalties, history and draw counter.  ``sampling=`` beside an ordinary ``sample_fn`` raises
+    ``ValueError``.
+
     Not here: preemption or swapping when the pool is full (``admit`` / ``step`` raise), prefix sharing, batched
     prefill without ``prefill_chunk`` (a prompt is then prefilled alone), prefill chunks interleaved with decode steps
     inside the captured step."""
@@ -273,9 +284,18 @@ class ContinuousBatchDecoder:
     def __init__(self, module: Any, max_batch: int, page_size: int = 64, max_pages: int = 1,
                  num_pages: Optional[int] = None, sample_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
                  skinny_gemm: bool = False, kv_cache: Optional[str] = None, use_cuda_graph: bool = False,
-                 record_steps: int = 8, wide_batch: bool = False, prefill_chunk: Optional[int] = None) -> None:
-        from .sample import sample_argmax
+                 record_steps: int = 8, wide_batch: bool = False, prefill_chunk: Optional[int] = None,
+                 sampling: Union[None, bool, SamplingParams] = None) -> None:
+        from .sample import RequestSampler, sample_argmax
 
+        if sampling is not None and not isinstance(sampling, (bool, SamplingParams)):
+            raise ValueError("ContinuousBatchDecoder: sampling must be None, a bool or the default SamplingParams, got "
+                             f"{type(sampling).__name__}")
+        if sampling is not None and sampling is not False and sample_fn is not None \
+                and not isinstance(sample_fn, RequestSampler):
+            raise ValueError("ContinuousBatchDecoder: sampling= needs a RequestSampler (or no sample_fn: one is built), "
+                             "an ordinary sample_fn treats the batch as one request")
+        self.default_sampling = (sampling if isinstance(sampling, SamplingParams) else SamplingParams()).check()
         self.module = module
         if prefill_chunk is not None and (not isinstance(prefill_chunk, int) or isinstance(prefill_chunk, bool)
                                           or prefill_chunk <= 0 or prefill_chunk % 32):
@@ -328,6 +348,15 @@ class ContinuousBatchDecoder:
         self.batch = TextDatasetBatch(input_token_ids=self.tok, position_ids=self.state.pos.view(B, 1),
                                       cumulative_seq_lengths=cu_q, cumulative_seq_lengths_padded=cu_q,
                                       inference_settings=settings)
+        if sample_fn is None and sampling is not None and sampling is not False:
+            sample_fn = RequestSampler(B, self.state.capacity, dev)
+        self.request_sampling = isinstance(sample_fn, RequestSampler)
+        if self.request_sampling:
+            if sample_fn.max_batch != B or sample_fn.history < self.state.capacity \
+                    or sample_fn.table.buf.device != self.tok.device:
+                raise ValueError(f"ContinuousBatchDecoder: the RequestSampler must have {B} rows and a history of at "
+                                 f"least max_pages * page_size = {self.state.capacity} on the model's device")
+            sample_fn.clear()  # warm-up and capture run over parked rows: they draw nothing and advance nothing
         self.sample_fn = sample_fn if sample_fn is not None else sample_argmax
         self.record_steps = int(record_steps)
         self._slot = torch.zeros(1, dtype=torch.long, device=dev)
@@ -387,17 +416,51 @@ class ContinuousBatchDecoder:
     def free_rows(self) -> list[int]:
         return [b for b, r in enumerate(self.rows) if r is None]
 
-    def admit(self, row: int, input_tokens: Sequence[int], max_tokens: int, index: Any = None) -> _Request:
+    def _sampling_of(self, sampling: SamplingArg, n: int) -> list:
+        """The checked ``SamplingParams`` of ``n`` requests being admitted: ``sampling`` is None (the decoder's
+        default), one for all, or one per request."""
+        from .sample import per_request
+
+        if not self.request_sampling:
+            if sampling is not None:
+                raise ValueError("ContinuousBatchDecoder: sampling= needs a decoder built with a RequestSampler "
+                                 "(sample_fn=RequestSampler(...) or sampling=True)")
+            return [None] * n
+        return per_request(self.default_sampling if sampling is None else sampling, n, "ContinuousBatchDecoder")
+
+    @contextlib.contextmanager
+    def _row_taken(self, row: int) -> Any:
+        """Around the end of an admission, from the sampler's ``set_row`` to the request's record: if it raises, the
+        sampler's row is parked again, so that no active table row stays over a decoder row without a request."""
+        try:
+            yield
+        except BaseException:
+            if self.request_sampling:
+                self.sample_fn.clear_row(row)
+            raise
+
+    def _first_token(self, row: int, last: torch.Tensor, params: Any, prompt: Sequence[int]) -> torch.Tensor:
+        """The request's first token ``[1, 1]`` from its prefill logits ``last [1, 1, V]``; with a ``RequestSampler`` the
+        row's table entry is filled first and the draw runs on the one-row slice."""
+        if not self.request_sampling:
+            return self.sample_fn(last).reshape(1, 1).to(torch.long)
+        self.sample_fn.set_row(row, params, prompt)
+        return self.sample_fn.first(row, last).reshape(1, 1)
+
+    def admit(self, row: int, input_tokens: Sequence[int], max_tokens: int, index: Any = None,
+              sampling: SamplingArg = None) -> _Request:
         """Row ``row`` takes a request: the prompt is prefilled (eager, alone), its K/V copied into freshly allocated
         pages, the row's device state set and its first token drawn with one ``sample_fn`` call on the prefill logits.
         ``ValueError`` for a request that cannot fit ``max_pages`` pages or the model's sequence length, ``RuntimeError``
-        naming the pool size when the pool lacks the prompt's pages -- both before anything is written."""
+        naming the pool size when the pool lacks the prompt's pages -- both before anything is written.  ``sampling``
+        (with a ``RequestSampler``): the request's ``SamplingParams``; None takes the decoder's default."""
         if self.prefill_chunk is not None:
-            req = self.admit_many([row], [input_tokens], [max_tokens])[0]
+            req = self.admit_many([row], [input_tokens], [max_tokens], sampling=sampling)[0]
             req.index = index
             return req
         n = len(input_tokens)
         self._check_request(row, n, max_tokens)
+        params = self._sampling_of(sampling, 1)[0]
         pages = self.allocator.alloc(-(-(n + 1) // self.page_size))  # RuntimeError before anything is written
         settings = InferenceSettings(use_cache=True, reset_cache=True, cache_index=self.spare_index, embedding_layers=[-1])
         with torch.no_grad():
@@ -412,13 +475,14 @@ class ContinuousBatchDecoder:
                 assert isinstance(kv, KVCache) and kv.length == n
                 a.cache[0].load_row(row, kv, pages)
             last = out.activations[:, -1:, :]
-            first = self.sample_fn(last).reshape(1, 1).to(torch.long)
-            self.state.assign(row, pages, n)
-            self.tok[row : row + 1].copy_(first)
-        req = _Request(index, n, int(max_tokens), pages)
-        req.tokens.append(int(first.item()))
-        req.logits.append(last.reshape(1, -1))
-        self.rows[row] = req
+            with self._row_taken(row):
+                first = self._first_token(row, last, params, input_tokens)
+                self.state.assign(row, pages, n)
+                self.tok[row : row + 1].copy_(first)
+                req = _Request(index, n, int(max_tokens), pages)
+                req.tokens.append(int(first.item()))
+                req.logits.append(last.reshape(1, -1))
+                self.rows[row] = req
         return req
 
     def _check_request(self, row: int, n: int, max_tokens: int) -> None:
@@ -435,7 +499,7 @@ class ContinuousBatchDecoder:
             raise ValueError(f"ContinuousBatchDecoder.admit: row {row} holds a request (release it first)")
 
     def admit_many(self, rows: Sequence[int], prompts: Sequence[Sequence[int]],
-                   max_tokens: Union[int, Sequence[int]]) -> list[_Request]:
+                   max_tokens: Union[int, Sequence[int]], sampling: SamplingArg = None) -> list[_Request]:
         """Batched admission (requires ``prefill_chunk=C``): rows ``rows[i]`` take the requests (``prompts[i]``,
         ``max_tokens[i]``; one int serves all).  Every request is checked and all pages are allocated first -- a
         ``ValueError`` or the ``RuntimeError`` of an exhausted pool leaves everything as it was.  Pass j then forwards
@@ -445,7 +509,8 @@ class ContinuousBatchDecoder:
         ``len(rows) * C`` tokens.  After the last pass ``sample_fn`` is called once per request, in the order given --
         the calls of admitting the requests one by one -- and the rows' device state is set.  Until then the rows stay
         parked, so the captured step is not disturbed (``captures`` stays 1).  If a pass raises, all pages of the call
-        are freed and the rows re-parked."""
+        are freed and the rows re-parked.  ``sampling`` (with a ``RequestSampler``): one ``SamplingParams`` for all or
+        one per request; None takes the decoder's default."""
         if self.prefill_chunk is None:
             raise ValueError("ContinuousBatchDecoder.admit_many: batched admission needs prefill_chunk")
         rows, toks = [int(r) for r in rows], [list(p) for p in prompts]
@@ -456,6 +521,7 @@ class ContinuousBatchDecoder:
             return []
         for row, t, m in zip(rows, toks, limits):
             self._check_request(row, len(t), m)
+        params = self._sampling_of(sampling, len(rows))
         need = [-(-(len(t) + 1) // self.page_size) for t in toks]
         taken = self.allocator.alloc(sum(need))  # RuntimeError before anything is written
         pages = [taken[sum(need[:i]) : sum(need[: i + 1])] for i in range(len(rows))]
@@ -481,19 +547,22 @@ class ContinuousBatchDecoder:
             except BaseException:
                 for row in rows:
                     st.park(row)
+                    if self.request_sampling:
+                        self.sample_fn.clear_row(row)
                 self.allocator.free(taken)
                 raise
             finally:
                 st.chunk = None
             reqs = []
             for i, row in enumerate(rows):
-                first = self.sample_fn(last[i]).reshape(1, 1).to(torch.long)
-                st.assign(row, pages[i], len(toks[i]))
-                self.tok[row : row + 1].copy_(first)
-                req = _Request(None, len(toks[i]), limits[i], pages[i])
-                req.tokens.append(int(first.item()))
-                req.logits.append(last[i].reshape(1, -1))
-                self.rows[row] = req
+                with self._row_taken(row):
+                    first = self._first_token(row, last[i], params[i], toks[i])
+                    st.assign(row, pages[i], len(toks[i]))
+                    self.tok[row : row + 1].copy_(first)
+                    req = _Request(None, len(toks[i]), limits[i], pages[i])
+                    req.tokens.append(int(first.item()))
+                    req.logits.append(last[i].reshape(1, -1))
+                    self.rows[row] = req
                 reqs.append(req)
         return reqs
 
@@ -504,6 +573,8 @@ class ContinuousBatchDecoder:
             return None
         self.allocator.free(req.pages)
         self.state.park(row)
+        if self.request_sampling:
+            self.sample_fn.clear_row(row)
         self.tok[row : row + 1].zero_()
         self.rows[row] = None
         return req
@@ -536,11 +607,13 @@ class ContinuousBatchDecoder:
 
     # ------------------------------------------------------------------ the serving loop
     def serve(self, requests: Sequence[tuple[Sequence[int], int]], stop_tokens: Sequence[int],
-              check_every: int = 8) -> list[tuple[list[int], torch.Tensor]]:
+              check_every: int = 8, sampling: SamplingArg = None) -> list[tuple[list[int], torch.Tensor]]:
         """Runs ``requests`` = [(prompt tokens, max_tokens), ...] to completion, in arrival order: free rows are filled,
         all rows step, and every ``check_every`` steps (fewer when a row would pass its ``max_tokens``) the recorded
         tokens are read back; a request is cut at its first stop token or its ``max_tokens``, its row released and
-        refilled.  Returns (tokens, logits ``[len(tokens), V]``) per request, in request order."""
+        refilled.  Returns (tokens, logits ``[len(tokens), V]``) per request, in request order.  ``sampling`` (with a
+        ``RequestSampler``): one ``SamplingParams`` for all or one per request."""
+        params = self._sampling_of(sampling, len(requests))
         stops = set(int(t) for t in stop_tokens)
         check_every = max(1, min(int(check_every), self.record_steps))
         results: list[Optional[tuple[list[int], torch.Tensor]]] = [None] * len(requests)
@@ -559,7 +632,8 @@ class ContinuousBatchDecoder:
             while self.prefill_chunk is not None and len(self.free_rows) > 1 and len(requests) - nxt > 1:
                 free = self.free_rows[: len(requests) - nxt]
                 batch = requests[nxt : nxt + len(free)]
-                reqs = self.admit_many(free, [t for t, _ in batch], [m for _, m in batch])
+                reqs = self.admit_many(free, [t for t, _ in batch], [m for _, m in batch],
+                                       sampling=params[nxt : nxt + len(free)] if self.request_sampling else None)
                 for row, req in zip(free, reqs):
                     req.index = nxt
                     nxt += 1
@@ -568,7 +642,7 @@ class ContinuousBatchDecoder:
             for row in self.free_rows:
                 while nxt < len(requests) and self.rows[row] is None:
                     toks, mt = requests[nxt]
-                    req = self.admit(row, toks, mt, index=nxt)
+                    req = self.admit(row, toks, mt, index=nxt, sampling=params[nxt])
                     nxt += 1
                     if over(req):  # done with the prefill's token
                         finish(row)

@@ -4,7 +4,7 @@ without the KV cache."""
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Any, Callable, Optional, Sequence
+from typing import Any, Callable, Optional, Sequence, Union
 
 import torch
 import yaml
@@ -18,7 +18,7 @@ from ..data.inference_settings import InferenceSettings
 from ..model.layers.base import TransformerLayerIO
 from ..model.model import get_transformer_layer_specs
 from ..tokenizer import Tokenizer
-from .sample import sample_argmax
+from .sample import SamplingParams, sample_argmax
 
 
 class CompletionOutput:
@@ -263,6 +263,7 @@ class TransformerInferenceModule(InferenceModule):
         from ...core.nn.attention.attention import check_kv_cache_scheme
 
         check_kv_cache_scheme(kv_cache, "generate")
+        self._refuse_request_sampler(sample_fn, "generate")
         if kv_cache is not None and not use_cuda_graph:
             raise ValueError("generate: kv_cache needs use_cuda_graph=True (the eager loop keeps a growing bf16 KV cache); "
                              "generate_batch takes kv_cache with and without the graph")
@@ -317,6 +318,7 @@ class TransformerInferenceModule(InferenceModule):
         from ...core.nn.attention.attention import ParallelSelfAttention, check_kv_cache_scheme, check_page_size
         from .batch_decode import BatchDecoder
 
+        self._refuse_request_sampler(sample_fn, "generate_batch")
         if page_size is not None:
             check_page_size(page_size, "generate_batch")
 
@@ -437,13 +439,16 @@ class TransformerInferenceModule(InferenceModule):
 
     def continuous_decoder(self, max_batch: int, page_size: int = 64, max_pages: int = 1,
                            num_pages: Optional[int] = None,
-                           sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
+                           sample_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
                            use_cuda_graph: bool = False, skinny_gemm: bool = False,
                            kv_cache: Optional[str] = None, record_steps: int = 8, wide_batch: bool = False,
-                           prefill_chunk: Optional[int] = None) -> Any:
+                           prefill_chunk: Optional[int] = None,
+                           sampling: Union[None, bool, SamplingParams] = None) -> Any:
         """The ``batch_decode.ContinuousBatchDecoder`` of this model for a serving loop (``admit`` / ``step`` /
         ``release``, or ``serve``): ``max_batch`` rows over a paged KV cache whose requests take at most ``max_pages``
-        pages of ``page_size`` tokens; captured once when ``use_cuda_graph``.  See ``generate_continuous``."""
+        pages of ``page_size`` tokens; captured once when ``use_cuda_graph``.  ``sample_fn=None`` is ``sample_argmax``;
+        ``sampling`` (True, or the default ``SamplingParams``) builds a ``sample.RequestSampler`` for per-request
+        sampling.  See ``generate_continuous``."""
         from .batch_decode import ContinuousBatchDecoder
 
         if self.devices is None or len(self.devices) != 1:
@@ -451,15 +456,17 @@ class TransformerInferenceModule(InferenceModule):
         return ContinuousBatchDecoder(self, max_batch, page_size=page_size, max_pages=max_pages, num_pages=num_pages,
                                       sample_fn=sample_fn, skinny_gemm=skinny_gemm, kv_cache=kv_cache,
                                       use_cuda_graph=use_cuda_graph, record_steps=record_steps, wide_batch=wide_batch,
-                                      prefill_chunk=prefill_chunk)
+                                      prefill_chunk=prefill_chunk, sampling=sampling)
 
     def generate_continuous(self, max_tokens: Any, input_texts: Optional[Sequence[str]] = None,
                             input_tokens: Optional[Sequence[Sequence[int]]] = None, max_batch: int = 4,
                             page_size: int = 64, num_pages: Optional[int] = None,
-                            sample_fn: Callable[[torch.Tensor], torch.Tensor] = sample_argmax,
+                            sample_fn: Optional[Callable[[torch.Tensor], torch.Tensor]] = None,
                             stop_tokens: Optional[Sequence[int]] = None, use_cuda_graph: bool = False,
                             skinny_gemm: bool = False, kv_cache: Optional[str] = None,
-                            wide_batch: bool = False, prefill_chunk: Optional[int] = None) -> list[CompletionOutput]:
+                            wide_batch: bool = False, prefill_chunk: Optional[int] = None,
+                            sampling: Union[None, SamplingParams, Sequence[SamplingParams]] = None
+                            ) -> list[CompletionOutput]:
         """Completions for N requests (N may exceed ``max_batch``) by continuous batching over a paged KV cache:
         ``max_batch`` rows share every decode step, and a row whose request reaches a stop token or its own
         ``max_tokens`` (an int, or one int per request) is refilled with the next request while the others go on
@@ -472,6 +479,13 @@ class TransformerInferenceModule(InferenceModule):
         whole stream and has ``generate_batch``'s limits on ``max_batch`` (4, 16 with ``skinny_gemm``, 64 with
         ``wide_batch``); ``kv_cache`` as in ``generate_batch``.  Greedy completions equal ``generate``'s per prompt up to the rounding of the batched
         kernels; with a seeded ``Sampler`` a draw depends on the row and the step a request happens to occupy.
+
+        ``sampling`` (one ``sample.SamplingParams`` for all requests, or one per request; not together with an ordinary
+        ``sample_fn``: ``ValueError``) samples per request through a ``sample.RequestSampler``: every request has its
+        own temperature (0: greedy), top-k, top-p, seed, repetition and presence penalty, its draws are a hash of its
+        own ``(seed, draw number)`` and its penalties see its own tokens only, so its text depends neither on the row,
+        nor on the neighbours, nor on the moment of its admission.  Still one launch per step inside the captured
+        graph (``ops.sample.sample_rows``).
 
         ``prefill_chunk=C`` (a positive multiple of 32, else ``ValueError``): every prompt is prefilled in chunks of at
         most ``C`` tokens straight into its pages (``ContinuousBatchDecoder``); with an FP8 KV cache the prompt's later
@@ -489,6 +503,12 @@ class TransformerInferenceModule(InferenceModule):
             raise ValueError("generate_continuous: max_tokens must be an int or one int per request")
         if any(len(p) == 0 for p in input_tokens) or any(m < 1 for m in limits):
             raise ValueError("generate_continuous: empty prompt or max_tokens < 1")
+        from .sample import RequestSampler, per_request
+
+        if sampling is not None and sample_fn is not None and not isinstance(sample_fn, RequestSampler):
+            raise ValueError("generate_continuous: sampling= cannot be combined with an ordinary sample_fn")
+        if sampling is not None:
+            sampling = per_request(sampling, len(input_tokens), "generate_continuous")
         if stop_tokens is None:
             assert self.tokenizer is not None, "If no tokenizer is provided, a stop token needs to be set manually"
             stop_tokens = [self.tokenizer.eos_token_id]
@@ -499,12 +519,20 @@ class TransformerInferenceModule(InferenceModule):
         dec = self.continuous_decoder(max_batch, page_size=page_size, max_pages=-(-longest // page_size),
                                       num_pages=num_pages, sample_fn=sample_fn, use_cuda_graph=use_cuda_graph,
                                       skinny_gemm=skinny_gemm, kv_cache=kv_cache, wide_batch=wide_batch,
-                                      prefill_chunk=prefill_chunk)
+                                      prefill_chunk=prefill_chunk, sampling=None if sampling is None else True)
         outs = []
-        for tokens, logits in dec.serve(list(zip(input_tokens, limits)), stop_tokens):
+        for tokens, logits in dec.serve(list(zip(input_tokens, limits)), stop_tokens, sampling=sampling):
             text = self.tokenizer.decode(tokens) if self.tokenizer is not None else None
             outs.append(CompletionOutput(completion_text=text, completion_tokens=tokens, completion_logits=logits))
         return outs
+
+    @staticmethod
+    def _refuse_request_sampler(sample_fn: Any, where: str) -> None:
+        from .sample import RequestSampler
+
+        if isinstance(sample_fn, RequestSampler):
+            raise ValueError(f"{where}: a RequestSampler serves generate_continuous / ContinuousBatchDecoder only (the "
+                             "static-batch decoders rewind live rows after capture)")
 
     def _generate_graph(self, prompt: TextDatasetBatch, n_in: int, max_tokens: int,
                         sample_fn: Callable[[torch.Tensor], torch.Tensor], stop_tokens: Sequence[int],
